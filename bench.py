@@ -2,7 +2,7 @@
 """bench.py -- the north-star measurement: Gelem/s and %HBM-roofline of a 64 Mi-element DiffArray
 forward + backward() on MI355X (BASELINE.json: metric / configs[2]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3b|cfg3a|cfg2] [--n 67108864]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3b|cfg3a|cfg2] [--n 67108864] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic input that is already resident in HBM:
 
@@ -115,6 +115,11 @@ def parse():
     ap.add_argument("--deterministic", action="store_true", help="bit-reproducible fp scatter_add (sorted path)")
     ap.add_argument("--eager", action="store_true", help="(default since round 4; kept for old command lines)")
     ap.add_argument("--dump-gradients", default=None, metavar="DIR", help="cfg3b: every rank saves what it holds of the table gradients after the exchange (owned slices when reduce-scattered) as DIR/grad_rank<r>.npz -- for the multi-rank parity tests")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, save what the last timed step handed its caller (the loss y and the step's arrays: "
+                         "gradients, image) as DIR/<name>.npy in float32 / float64, at most 64 MB in all: an output that does not fit its "
+                         "share is replaced by a fixed, seeded sample of its elements.  Inputs are the same on every run, so two builds "
+                         "compare output for output.  --gpus 1 only")
     ap.add_argument("--graph", action="store_true", help="ALSO time the K steps as replays of a captured step graph (graph_ms_per_step); `value` stays the python-driven protocol")
     ap.add_argument("--allreduce-grads", action="store_true",
                     help="(default since round 5: what BASELINE.json's north_star names) multi-GPU: all-reduce the table gradients, every rank ends up with all K bins")
@@ -127,7 +132,12 @@ def parse():
     # ranks started by relaunch_as_ranks() receive the original command line through the environment: torch.distributed.run parses
     # its own options with prefix matching, and a script argument like `--n` is ambiguous to it
     forwarded = os.environ.get("ENOKI_BENCH_ARGV")
-    return ap.parse_args(json.loads(forwarded)) if forwarded is not None else ap.parse_args()
+    args = ap.parse_args(json.loads(forwarded)) if forwarded is not None else ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (ms_per_step is the timed region over --steps)")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs saves the outputs of one process: use it with --gpus 1")
+    return args
 
 
 PMC_FILE = os.path.join("profiles", "rocprof_pmc_r06.txt")
@@ -644,6 +654,10 @@ class Bench:
             # `value` is ALWAYS the python-driven protocol (what a caller of the library gets); the replay time is reported next to it
             ms_per_step = eager_ms
             replay = "eager (python-driven steps: tape walk, allocator, one launch call per kernel); graph_ms_per_step is the hipGraph replay of the same step"
+        # --dump-outputs: the last step of the loop that ms_per_step times, copied to the host before the profiled steps below run
+        dumped = None
+        if self.args.dump_outputs and workload == self.args.workload:
+            dumped = caller_outputs(out)
         gelem_s = units / (ms_per_step * 1e-3) / 1e9
         # per-kernel timing of the same step (run eagerly): one HIP event per launch on the library stream
         torch.cuda.synchronize()
@@ -708,6 +722,8 @@ class Bench:
             else:
                 np.savez(os.path.join(self.args.dump_gradients, f"grad_rank{self.rank}.npz"), gA=out["gA"].numpy(), gB=out["gB"].numpy(),
                          begin=0, end=K_TABLE)
+        if dumped is not None:
+            write_outputs(self.args.dump_outputs, dumped)
         outputs = {k: out[k].numpy() for k in ("gA", "gB", "ga", "gb") if k in out} if self.world == 1 and workload == self.args.workload else {}
         outputs["y"] = y_val
         if roofline:
@@ -720,6 +736,29 @@ class Bench:
                 "graph_ms_per_step": round(graph_ms, 4) if graph_ms is not None else None, "result_y": y_val,
                 "roofline": roofline, "collectives_per_step": coll_per_step,
                 "outputs": outputs, "replay": replay}
+
+
+DUMP_BYTES = 64 * 10 ** 6        # --dump-outputs: all files of one run together
+
+
+def caller_outputs(out):
+    """host copies of what one step hands its caller: the loss `y` and the step's arrays (table gradients, image)"""
+    return {k: out[k].numpy() for k in ("y", "gA", "gB", "ga", "gb", "grad", "image") if k in out}
+
+
+def write_outputs(directory, arrays):
+    """DIR/<name>.npy per output, float32 / float64, DUMP_BYTES in all; an output larger than its share is replaced by the
+    elements at a fixed, seeded, sorted choice of positions (the same positions on every run)"""
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BYTES // len(arrays) - 1024          # (1024: the .npy header)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a).reshape(-1)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        keep = share // a.itemsize
+        if a.size > keep:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def cpu_baseline(workload, N):

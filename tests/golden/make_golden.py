@@ -237,3 +237,46 @@ rng = np.random.default_rng(80)
 sd = rng.standard_normal((3, 1024)); sd = (sd / np.linalg.norm(sd, axis=0)).astype(np.float32)
 np.savez_compressed(os.path.join(HERE, "sh.npz"), d=sd, out=R.sh(sd, 9))
 
+
+# ---- the reference side of tests that compare with the live build where it exists (test_tape_parity.py, test_random.py,
+# test_sphere_gpu.py): the same programs on the same inputs, so that a checkout without the reference build runs them too
+import hashlib  # noqa: E402
+from test_tape_parity import GATHER_SEEDS, SEEDS  # noqa: E402
+from test_random import CASES, INITSTATE, KEYS, pcg32_inputs  # noqa: E402
+from test_sphere_gpu import SCENES  # noqa: E402
+
+
+def tape_entries(prefix, v, g):
+    out = {prefix + "value": v, prefix + "n_grads": np.array(len(g))}
+    for i, gi in enumerate(g):
+        if gi is not None:
+            out[f"{prefix}g{i}"] = gi
+    return out
+
+
+rv = {}
+for seed in SEEDS:
+    for mode in ("backward", "forward"):
+        rv.update(tape_entries(f"s{seed}_{mode}__", *tape_lib.run(tape_lib.ref_fn(), tape_lib.random_program(seed, mode=mode))))
+np.savez_compressed(os.path.join(HERE, "tape_random_vertical.npz"), **rv)
+rg = {}
+for seed in GATHER_SEEDS:
+    rg.update(tape_entries(f"s{seed}__", *tape_lib.run(tape_lib.ref_fn(), tape_lib.random_gather_program(seed))))
+np.savez_compressed(os.path.join(HERE, "tape_random_gather.npz"), **rg)
+np.savez_compressed(os.path.join(HERE, "tape_cfg3a_big.npz"),
+                    **tape_entries("", *tape_lib.run(tape_lib.ref_fn(), tape_lib.suite(n=100003)["cfg3a"])))
+
+# PCG32: bit-exact comparisons only, so the SHA-256 of every output array stands in for its bytes (the largest case is 5 MB)
+pd = {}
+for n, steps, bound, delta in CASES:
+    seq, mask = pcg32_inputs(n)
+    r = R.pcg32(INITSTATE, seq, steps, mask, bound, delta)
+    for k in KEYS:
+        pd[f"{n}_{steps}_{bound}_{delta}_{k}"] = np.array(hashlib.sha256(np.ascontiguousarray(r[k]).tobytes()).hexdigest())
+np.savez_compressed(os.path.join(HERE, "pcg32_cases.npz"), **pd)
+
+sc = {}
+for res in SCENES:
+    img, h = run(R.lib.ref_cfg4, *scene(res))
+    sc[f"res{res}_image"], sc[f"res{res}_hits"] = img, np.array(h)
+np.savez_compressed(os.path.join(HERE, "cfg4_scenes.npz"), **sc)

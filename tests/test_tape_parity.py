@@ -1,9 +1,10 @@
 """Tape / DiffArray parity.
 
 CPU (not gpu):  product Tape<T> + DiffArray<T> instantiated over the oracle array type (tests/cpp/tape_host.cpp)
-                vs the UNMODIFIED reference build (oracle/_ref) -- bit-for-bit on every program except the ones whose
-                edge weights go through rcp/rsqrt (class C: the AVX2 reference uses rcpps + Newton).  This pins the
-                host logic of the tape: graph bookkeeping, sweep order, refcounting, specials, simplification.
+                vs the UNMODIFIED reference build (oracle/_ref, else the fixtures it made under tests/golden/) --
+                bit-for-bit on every program except the ones whose edge weights go through rcp/rsqrt (class C: the
+                AVX2 reference uses rcpps + Newton).  This pins the host logic of the tape: graph bookkeeping, sweep
+                order, refcounting, specials, simplification.
 GPU  (gpu):     product Tape over HIPArray<float> (tests/cpp/tape_hip.cpp -> libenoki-hip-autodiff.so -> C ABI)
                 vs the reference build when it travelled with the tree, else vs the committed fixtures in
                 tests/golden/tape_*.npz (generated from the reference build by tests/golden/make_golden.py).
@@ -21,13 +22,15 @@ GOLDEN = os.path.join(tl.HERE, "golden")
 NAMES = sorted(tl.suite().keys())
 
 
-def reference_result(name, prog):
-    """reference outputs for a suite program: live from oracle/_ref when present, else the golden fixture"""
+def reference_result(name, prog, fixture=None, key=""):
+    """reference outputs for a program: live from oracle/_ref when present, else the golden fixture made from that build
+    (tests/golden/<fixture or tape_<name>>.npz; `key` picks one program of a fixture that holds several)"""
     if HAVE_REF:
         return tl.run(tl.ref_fn(), prog)
-    z = np.load(os.path.join(GOLDEN, f"tape_{name}.npz"))
-    grads = [z[f"g{i}"] if f"g{i}" in z else None for i in range(int(z["n_grads"]))]
-    return z["value"], grads
+    z = np.load(os.path.join(GOLDEN, f"{fixture or 'tape_' + name}.npz"))
+    p = key + "__" if key else ""
+    grads = [z[f"{p}g{i}"] if f"{p}g{i}" in z else None for i in range(int(z[f"{p}n_grads"]))]
+    return z[f"{p}value"], grads
 
 
 @pytest.mark.skipif(not HAVE_REF, reason="oracle/_ref was not built (needs /root/reference)")
@@ -152,9 +155,7 @@ def test_hip_tape_matches_reference(name):
 def test_hip_cfg3a_gradients_bit_exact_elementwise():
     """cfg3a: the gradients are purely elementwise given the seed -> bit-exact even though y = hsum(..) is not"""
     prog = tl.suite(n=100003)["cfg3a"]
-    rv, rg = reference_result("cfg3a_big", prog) if HAVE_REF else (None, None)
-    if not HAVE_REF:
-        pytest.skip("needs the reference build for n = 100003")
+    rv, rg = reference_result("cfg3a_big", prog)
     gv, gg = tl.run(tl.hip_lib().hip_tape_program, prog)
     assert bits_equal(rg[0], gg[0]) and bits_equal(rg[2], gg[2])
     from conftest import hsum_bound, hsum_depth, stat_sum_bound
@@ -182,12 +183,11 @@ def same_grads(ref, got, prog):
     return True
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="oracle/_ref was not built (needs /root/reference)")
 @pytest.mark.parametrize("seed", SEEDS)
 def test_random_vertical_programs_host_tape_vs_reference(seed):
     for mode in ("backward", "forward"):
         prog = tl.random_program(seed, mode=mode)
-        rv, rg = tl.run(tl.ref_fn(), prog)
+        rv, rg = reference_result(None, prog, "tape_random_vertical", f"s{seed}_{mode}")
         hv, hg = tl.run(tl.host_lib().host_tape_program, prog)
         assert bits_equal(rv, hv), (seed, mode)
         assert same_grads(rg, hg, prog) if mode == "backward" else bits_equal(rg[0], hg[0]), (seed, mode)
@@ -272,11 +272,11 @@ def _values_equal(ref, got):
     return all((a is None and b is None) or (a is not None and b is not None and np.array_equal(a, b)) for a, b in zip(rg, gg))
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="oracle/_ref was not built (needs /root/reference)")
 @pytest.mark.parametrize("seed", GATHER_SEEDS)
 def test_random_gather_programs_host_tape_vs_reference(seed):
     prog = tl.random_gather_program(seed)
-    assert _all_equal(tl.run(tl.ref_fn(), prog), tl.run(tl.host_lib().host_tape_program, prog)), seed
+    ref = reference_result(None, prog, "tape_random_gather", f"s{seed}")
+    assert _all_equal(ref, tl.run(tl.host_lib().host_tape_program, prog)), seed
     assert tl.host_lib().host_tape_live_nodes() == 0
 
 
