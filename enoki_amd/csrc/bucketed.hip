@@ -439,8 +439,11 @@ Bucketed::~Bucketed() {
         r.clean[meta_slot] = meta_clean;
         meta = nullptr;
     }
-    for (void *p : { meta, pair_idx, x_b, u_b, m_b, early, page_lists })
+    for (void *p : { meta, early, page_lists })
         if (p) ek_hip_free(p);
+    if (!owner)
+        for (void *p : { pair_idx, x_b, u_b, m_b })
+            if (p) ek_hip_free(p);
 }
 
 static size_t bucket_target_pieces(size_t n, int n_buckets) {
@@ -511,15 +514,34 @@ static int bucketed_create(Bucketed *b, const T *x, const I *index) {
 
 /// A table of three or more slices: (index, x) are first split by SLICE into contiguous runs -- the count / scan / partition
 /// kernels of ek_binned.h with 32-bit slice-local indices -- so that every slice's page partition reads only its own elements
-/// (20 B/elt once instead of 8 B/elt per slice).  The slice populations come back to the host (which sizes the per-slice work).
+/// (20 B/elt once instead of 8 B/elt per slice).  The slice populations stay on the device: slice s owns elements
+/// [range[2 s], range[2 s] + range[2 s + 1]) of the split's output (runs start at multiples of 4 elements, so that the slices'
+/// partitions load 16-byte vectors), and everything that follows reads its size from there -- no read-back, the split can be part
+/// of a captured step graph.
 struct CoarseSplit {
-    void *idx = nullptr, *x = nullptr, *meta = nullptr;      // slice-local indices and x in slice order; counts / bases
-    std::vector<uint32_t> base;                              // host copy of bucket_base[0 .. S]
+    void *idx = nullptr, *x = nullptr, *meta = nullptr;      // slice-local indices and x in slice order; counts / bases / ranges
+    uint32_t *range = nullptr;                               // device: [S][2] first element, element count
+    size_t elements = 0;                                     // what idx / x hold, the alignment gaps included
     ~CoarseSplit() {
         for (void *p : { idx, x, meta })
             if (p) ek_hip_free(p);
     }
 };
+
+// the runs of the split: slice s from a multiple of 4 elements on (bucket_base: where k_bin_partition places them)
+static __global__ __launch_bounds__(64) void k_slice_ranges(uint32_t *__restrict__ range, uint32_t *__restrict__ bucket_base,
+                                                             const uint32_t *__restrict__ row_total, int S) {
+    if (threadIdx.x != 0) return;
+    uint32_t first = 0;
+    for (int s = 0; s < S; ++s) {
+        const uint32_t cnt = row_total[s];
+        bucket_base[s] = first;
+        range[2 * s] = first;
+        range[2 * s + 1] = cnt;
+        first += (cnt + 3u) & ~3u;
+    }
+    bucket_base[S] = first;
+}
 
 template <int Shift>
 static int coarse_split(CoarseSplit &cs, const float *x, const uint32_t *index, const Arg<uint8_t> &mask, size_t n, int S) {
@@ -534,15 +556,17 @@ static int coarse_split(CoarseSplit &cs, const float *x, const uint32_t *index, 
     int rep_shift = 0;
     while ((S << (rep_shift + 1)) <= kMaxBuckets && rep_shift < 4) ++rep_shift;
     const size_t count_entries = (size_t) S * blocks;
-    if (int rc = ek_hip_malloc((count_entries + 2 * kMaxBuckets + 2) * sizeof(uint32_t), &cs.meta)) return rc;
-    if (int rc = ek_hip_malloc(n * sizeof(uint32_t), &cs.idx)) return rc;
-    if (int rc = ek_hip_malloc(n * sizeof(float), &cs.x)) return rc;
+    cs.elements = n + 4 * (size_t) S;
+    if (int rc = ek_hip_malloc((count_entries + 4 * kMaxBuckets + 2) * sizeof(uint32_t), &cs.meta)) return rc;
+    if (int rc = ek_hip_malloc(cs.elements * sizeof(uint32_t), &cs.idx)) return rc;
+    if (int rc = ek_hip_malloc(cs.elements * sizeof(float), &cs.x)) return rc;
     uint32_t *counts = (uint32_t *) cs.meta, *row_total = counts + count_entries, *bucket_base = row_total + kMaxBuckets;
+    cs.range = bucket_base + kMaxBuckets + 2;
     hipLaunchKernelGGL((k_bin_count<uint32_t, Shift>), dim3(blocks), dim3(kThreads), 0, c.stream, counts, index, mask, n, chunk, S,
                        rep_shift, vec_ok);
     EK_LAUNCH_CHECK("bucket_slice_count", n, n * sizeof(uint32_t) + arg_bytes(mask, n));
     hipLaunchKernelGGL(k_bin_scan_rows, dim3(S), dim3(1024), 0, c.stream, counts, row_total, blocks);
-    hipLaunchKernelGGL(k_bin_scan_buckets, dim3(1), dim3(256), 0, c.stream, bucket_base, (uint32_t *) nullptr, (const uint32_t *) row_total, S, 0u);
+    hipLaunchKernelGGL(k_slice_ranges, dim3(1), dim3(64), 0, c.stream, cs.range, bucket_base, (const uint32_t *) row_total, S);
     EK_LAUNCH_CHECK("bucket_slice_scan", count_entries, 2 * count_entries * sizeof(uint32_t));
     BinStreams<float, 1> st;
     st.value[0] = Arg<float>{ x, 0.f, 1u };
@@ -554,25 +578,36 @@ static int coarse_split(CoarseSplit &cs, const float *x, const uint32_t *index, 
                        (uint32_t *) cs.idx, st, (const uint32_t *) counts, (const uint32_t *) bucket_base, index, mask, n, chunk, S, 0,
                        vec_ok);
     EK_LAUNCH_CHECK("bucket_slice_partition", n, n * 16 + arg_bytes(mask, n));
-    cs.base.resize(S + 1);
-    EK_HIP_CHECK(hipMemcpyAsync(cs.base.data(), bucket_base, (S + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
-    EK_HIP_CHECK(hipStreamSynchronize(c.stream));
     return EK_OK;
 }
+
+/// One slice of a split table (CoarseSplit): its range and its pages are known on the device only.  The slices share ONE page pool
+/// (the owner's pair_idx / x_b and full-page lists, paged_slice_pool_pages()) and the partition's working lists; `plan` is the
+/// geometry of all of them (256 buckets, the whole input's element count as the bound).
+struct PagedSlice {
+    const uint32_t *range;         // device: [first element, element count] of the slice in the split's output
+    uint32_t page0;                // s * paged_slice_gap()
+    const PagedPlan *plan;
+    Bucketed *owner;
+    uint32_t *glist_full;          // the pool's full-page lists
+    uint32_t *work;                // wdir | wlist (pool pages each) | cnt_full | loff | part ([kMaxBuckets][W] each)
+    size_t pool_pages;
+};
 
 /// The same object from the single-pass paged partition (ek_paged.h): 4-byte element types, n <= 2^30.  One streaming pass
 /// over (index, x) + the page directory: no count pass, no scans.
 template <typename I>
-static int bucketed_create_paged(Bucketed *b, const float *x, const I *index, const Arg<uint8_t> &mask, int shift) {
+static int bucketed_create_paged(Bucketed *b, const float *x, const I *index, const Arg<uint8_t> &mask, int shift,
+                                 const PagedSlice *slice = nullptr) {
     RoctxRange range("enoki-hip: bucket partition (pages)");
     Context &c = ctx();
     b->shift = shift;
-    const size_t n = b->n;
+    const size_t n = b->n;             // (a slice: the bound, the whole input)
     const int n_buckets = b->n_buckets = (int) ((b->table_size + ((size_t) 1 << shift) - 1) >> shift);
-    const PagedPlan p = paged_plan(n, n_buckets, c.num_cu, c.tuning.xcd_balance != 0);
+    const PagedPlan p = slice ? *slice->plan : paged_plan(n, n_buckets, c.num_cu, c.tuning.xcd_balance != 0);
     if (p.W > 1024) return fail(EK_ERR_UNSUPPORTED, "ek_hip_bucketed_pair_create(): %u workgroups", p.W);
     b->page_shift = p.page_shift;
-    b->positions = p.page_slots << p.page_shift;
+    b->positions = slice ? slice->pool_pages << p.page_shift : p.page_slots << p.page_shift;
     const uint32_t target_pieces = (uint32_t) bucket_target_pieces(n, n_buckets);
     b->max_pieces = target_pieces + (unsigned) n_buckets;
     // meta: page totals [kPgReplicas][2][256] + meta row [256] (kPgCounterWords) | base_full[257] | base_part[257] | piece_prefix[257] | reduce partials
@@ -596,12 +631,21 @@ static int bucketed_create_paged(Bucketed *b, const float *x, const I *index, co
     }
     if (b->meta_slot < 0)
         if (int rc = ek_hip_malloc(meta_words * sizeof(uint32_t) + (size_t) b->max_pieces * 16 + 16, &b->meta)) return rc;
-    if (int rc = ek_hip_malloc(b->positions * sizeof(uint16_t), &b->pair_idx)) return rc;
-    if (int rc = ek_hip_malloc(b->positions * sizeof(float), &b->x_b)) return rc;
     const size_t part_entries = (size_t) p.W * n_buckets;
-    if (int rc = ek_hip_malloc((p.page_slots + part_entries + 1) * sizeof(uint32_t), &b->page_lists)) return rc;
-    b->glist_full = (uint32_t *) b->page_lists;
-    b->glist_part = b->glist_full + p.page_slots;
+    if (slice) {
+        b->owner = slice->owner;
+        b->pair_idx = slice->owner->pair_idx;
+        b->x_b = slice->owner->x_b;
+        if (int rc = ek_hip_malloc((part_entries + 1) * sizeof(uint32_t), &b->page_lists)) return rc;
+        b->glist_full = slice->glist_full;
+        b->glist_part = (uint32_t *) b->page_lists;
+    } else {
+        if (int rc = ek_hip_malloc(b->positions * sizeof(uint16_t), &b->pair_idx)) return rc;
+        if (int rc = ek_hip_malloc(b->positions * sizeof(float), &b->x_b)) return rc;
+        if (int rc = ek_hip_malloc((p.page_slots + part_entries + 1) * sizeof(uint32_t), &b->page_lists)) return rc;
+        b->glist_full = (uint32_t *) b->page_lists;
+        b->glist_part = b->glist_full + p.page_slots;
+    }
     uint32_t *gtotal = (uint32_t *) b->meta;
     b->bucket_base = gtotal + kPgCounterWords;
     b->active = gtotal + kPgMetaBase + kPgMetaResult;        // (written by the directory launch from the partition's accumulators)
@@ -612,23 +656,27 @@ static int bucketed_create_paged(Bucketed *b, const float *x, const I *index, co
     b->reduce_partials = (void *) (((uintptr_t) (gtotal + meta_words) + 15) & ~(uintptr_t) 15);
     // what only the two kernels below need: the workgroups' own page lists and counts
     Scratch work;
-    if (int rc = work.alloc((2 * p.page_slots + 3 * part_entries) * sizeof(uint32_t))) return rc;
+    if (!slice)
+        if (int rc = work.alloc((2 * p.page_slots + 3 * part_entries) * sizeof(uint32_t))) return rc;
     PagedOut<float> out;
     out.lp = (uint16_t *) b->pair_idx;
     out.xp = (float *) b->x_b;
-    out.wdir = (uint32_t *) work.ptr;
-    out.wlist = out.wdir + p.page_slots;
-    out.cnt_full = out.wlist + p.page_slots;
+    const size_t list_slots = slice ? slice->pool_pages : p.page_slots;
+    out.wdir = slice ? slice->work : (uint32_t *) work.ptr;
+    out.wlist = out.wdir + list_slots;
+    out.cnt_full = out.wlist + list_slots;
     out.loff = out.cnt_full + part_entries;
     out.part = out.loff + part_entries;
     out.gtotal = gtotal;
     out.active = gtotal + kPgMetaBase + kPgMetaAccum;
     out.lo = b->win_lo; out.span = b->win_span ? b->win_span : (uint32_t) std::min<size_t>(b->table_size, 0xFFFFFFFFu);
+    out.range = slice ? slice->range : nullptr;
+    out.range_page0 = slice ? slice->page0 : 0u;
     // tiles dealt to the classes w % 8 by the weights the previous launches fed back (ek_paged.h); a launch of at least 32 tiles per
     // workgroup stamps its loops and lets the directory launch update the weights
     // (ENOKI_HIP_XCD_BALANCE=2: the slots are provisioned and the loops stamped, but the chunks stay equal -- what
     // ek_hip_partition_class_state() then reports is the imbalance itself)
-    uint32_t *class_block = p.balanced ? class_weights_or_null() : nullptr;
+    uint32_t *class_block = p.balanced && !slice ? class_weights_or_null() : nullptr;
     out.class_w = c.tuning.xcd_balance == 1 ? class_block : nullptr;
     const bool stamped = class_block && n >= (size_t) 32 * kPgTile * p.W && p.W <= 1024;
     const bool feedback = stamped && out.class_w;
@@ -649,7 +697,12 @@ static int bucketed_create_paged(Bucketed *b, const float *x, const I *index, co
         const size_t fixed_lds = want ? static_lds_of(kernel) : SIZE_MAX;
         if (fixed_lds != SIZE_MAX && fixed_lds + p.lds + (size_t) p.slots * sizeof(uint32_t) <= (size_t) 160 * 1024) {
             lds += (size_t) p.slots * sizeof(uint32_t);
-            out.wdir_lds = 1;
+            out.wdir_lds = slice ? p.slots : 1u;
+        } else if (slice && fixed_lds != SIZE_MAX && fixed_lds + p.lds + 1024 * sizeof(uint32_t) <= (size_t) 160 * 1024) {
+            // (a slice's slots are known on the device only: what the LDS has room for, each workgroup decides by its own count)
+            const size_t room = ((size_t) 160 * 1024 - fixed_lds - p.lds) / sizeof(uint32_t);
+            lds += room * sizeof(uint32_t);
+            out.wdir_lds = (uint32_t) room;
         }
         if (int rc = allow_big_lds(kernel, lds)) return rc;
         hipLaunchKernelGGL(kernel, dim3(p.W), dim3(kPgThreads), lds, c.stream, out, index, mask, x, n, p.chunk, n_buckets, shift,
@@ -657,14 +710,26 @@ static int bucketed_create_paged(Bucketed *b, const float *x, const I *index, co
         return EK_OK;
     };
     int rc;
-    if (p.page_shift == 6) rc = mask.vec ? launch(k_page_partition<float, I, 6, true>) : launch(k_page_partition<float, I, 6, false>);
+    if (slice) {
+        // (the pool's geometry: 32-element pages for every slice; the slices' input has no mask -- the split dropped those lanes)
+        if (p.page_shift != 5 || mask.vec) return fail(EK_ERR_INVALID, "bucketed_create_paged(): slice of an unexpected shape");
+        rc = launch(k_page_partition<float, I, 5, false, false, true>);
+    }
+    else if (p.page_shift == 6) rc = mask.vec ? launch(k_page_partition<float, I, 6, true>) : launch(k_page_partition<float, I, 6, false>);
     else rc = mask.vec ? launch(k_page_partition<float, I, 5, true>) : launch(k_page_partition<float, I, 5, false>);
     if (rc) return rc;
     EK_LAUNCH_CHECK("bucket_partition", n, n * (sizeof(I) + sizeof(float)) + arg_bytes(mask, n) + n * (sizeof(uint16_t) + sizeof(float)));
-    hipLaunchKernelGGL(k_page_directory, dim3(n_buckets, kPgDirSlices), dim3(256), 0, c.stream, b->glist_full, b->glist_part, b->bucket_base,
+    if (slice)
+        hipLaunchKernelGGL(k_page_directory<true>, dim3(n_buckets, kPgDirSlices), dim3(256), 0, c.stream, b->glist_full, b->glist_part, b->bucket_base,
+                           b->base_part, b->piece_prefix, gtotal, (const uint32_t *) out.cnt_full,
+                           (const uint32_t *) out.loff, (const uint32_t *) out.part, (const uint32_t *) out.wlist, p.W, p.slots, n_buckets,
+                           target_pieces, (uint32_t *) nullptr, (const uint32_t *) nullptr, band, slice->range, slice->page0, p.page_shift);
+    else
+    hipLaunchKernelGGL(k_page_directory<false>, dim3(n_buckets, kPgDirSlices), dim3(256), 0, c.stream, b->glist_full, b->glist_part, b->bucket_base,
                        b->base_part, b->piece_prefix, gtotal, (const uint32_t *) out.cnt_full,
                        (const uint32_t *) out.loff, (const uint32_t *) out.part, (const uint32_t *) out.wlist, p.W, p.slots, n_buckets,
-                       target_pieces, feedback ? class_state().weights() : (uint32_t *) nullptr, (const uint32_t *) out.class_stamp, band);
+                       target_pieces, feedback ? class_state().weights() : (uint32_t *) nullptr, (const uint32_t *) out.class_stamp, band,
+                       (const uint32_t *) nullptr, 0u, 0);
     EK_LAUNCH_CHECK("bucket_directory", p.page_slots, 2 * p.page_slots * sizeof(uint32_t));
     return EK_OK;
 }
@@ -682,8 +747,13 @@ static int bucketed_forward_launch(Bucketed *b, void *out, int map_op, bool keep
     const bool partner = keep && ROp != EK_REDUCE_NONE &&
                          ((map_op == EK_SIN && keep_op == EK_COS) || (map_op == EK_COS && keep_op == EK_SIN));
     void **kept = partner ? &b->m_b : &b->u_b;
-    if (keep && !*kept)
-        if (int rc = ek_hip_malloc(b->positions * sizeof(T), kept)) return rc;
+    if (keep && !*kept) {
+        // (a slice keeps its values in the owner's pool, at the positions of its own pages)
+        void **pool = b->owner ? (partner ? &b->owner->m_b : &b->owner->u_b) : kept;
+        if (!*pool)
+            if (int rc = ek_hip_malloc(b->positions * sizeof(T), pool)) return rc;
+        *kept = *pool;
+    }
     const int flip_a = b->flip_a(), flip_c = b->flip_c(), two = b->two_roundings();
     EK_BY_LAYOUT(b, {
         if (int rc = allow_big_lds(k_bucket_pair_forward<T, ROp, VV, PS>, lds)) return rc;
@@ -1063,10 +1133,10 @@ static int index_partition_run_paged(IndexPartition *ip, const uint32_t *index, 
     else rc = mask.vec ? launch(k_page_partition<float, uint32_t, 5, true, true>) : launch(k_page_partition<float, uint32_t, 5, false, true>);
     if (rc) return rc;
     EK_LAUNCH_CHECK("index_partition", n, n * 2 * sizeof(uint32_t) + arg_bytes(mask, n));
-    hipLaunchKernelGGL(k_page_directory, dim3(n_buckets, kPgDirSlices), dim3(256), 0, c.stream, glist_full, glist_part, base_full,
+    hipLaunchKernelGGL(k_page_directory<false>, dim3(n_buckets, kPgDirSlices), dim3(256), 0, c.stream, glist_full, glist_part, base_full,
                        base_part, piece_prefix, gtotal, (const uint32_t *) out.cnt_full, (const uint32_t *) out.loff,
                        (const uint32_t *) out.part, (const uint32_t *) out.wlist, p.W, p.slots, n_buckets, 0u,
-                       (uint32_t *) nullptr, (const uint32_t *) nullptr, kPgWeightBand);
+                       (uint32_t *) nullptr, (const uint32_t *) nullptr, kPgWeightBand, (const uint32_t *) nullptr, 0u, 0);
     EK_LAUNCH_CHECK("index_partition_directory", p.page_slots, 2 * p.page_slots * sizeof(uint32_t));
     ip->info.bucket_base = base_full;
     ip->info.local = (const uint32_t *) ip->local;
@@ -1126,7 +1196,6 @@ struct ek_hip_bucketed : ek::Bucketed {
     std::vector<ek_hip_bucketed *> slices;
     size_t slice_span = 0;
     bool slices_split = false;       // the slices hold disjoint parts of the input (CoarseSplit) instead of filtered views of all of it
-    bool empty_slice = false;        // a slice that received no element
     ~ek_hip_bucketed() { for (ek_hip_bucketed *s : slices) delete s; }
 };
 constexpr int kMaxSlices = 64;
@@ -1214,15 +1283,25 @@ int ek_hip_bucketed_pair_create_masked(int type, int index_type, int op, const v
             const int S = (int) ((table_size + span - 1) / span);
             b->slice_span = span;
             rc = EK_OK;
-            // two slices: each reads all of (index, x) and keeps its own; three or more: split by slice first (needs the slice
-            // populations on the host, which a captured step cannot wait for)
+            // two slices: each reads all of (index, x) and keeps its own; three or more: split by slice first, then every slice
+            // partitions its own run into ONE page pool -- sized from n and S alone, the runs' lengths stay on the device
             CoarseSplit cs;
             const bool split = S >= 3;
+            const int slice_shift = bin_shift_of<float> - (want_half ? 1 : 0);
+            PagedPlan pool_plan;
+            size_t pool_pages = 0;
+            Scratch pool_work;
             if (split) {
-                rc = refuse_while_capturing("ek_hip_bucketed_pair_create(): a table of three or more slices (slice populations are read back)");
-                if (rc == EK_OK)
-                    rc = want_half ? coarse_split<bin_shift_of<float> - 1 + 8>(cs, (const float *) x, (const uint32_t *) index, m, n, S)
-                                   : coarse_split<bin_shift_of<float> + 8>(cs, (const float *) x, (const uint32_t *) index, m, n, S);
+                rc = want_half ? coarse_split<bin_shift_of<float> - 1 + 8>(cs, (const float *) x, (const uint32_t *) index, m, n, S)
+                               : coarse_split<bin_shift_of<float> + 8>(cs, (const float *) x, (const uint32_t *) index, m, n, S);
+                // every slice with the geometry of a full one (256 buckets: 32-element pages) and the whole input as its bound
+                pool_plan = paged_plan(n, kMaxBuckets, ctx().num_cu);
+                pool_pages = paged_slice_pool_pages(cs.elements, S, pool_plan.W, pool_plan.page_shift);
+                b->positions = pool_pages << pool_plan.page_shift;
+                if (rc == EK_OK) rc = ek_hip_malloc(b->positions * sizeof(uint16_t), &b->pair_idx);
+                if (rc == EK_OK) rc = ek_hip_malloc(b->positions * sizeof(float), &b->x_b);
+                if (rc == EK_OK) rc = ek_hip_malloc(pool_pages * sizeof(uint32_t), &b->page_lists);
+                if (rc == EK_OK) rc = pool_work.alloc((2 * pool_pages + 3 * (size_t) pool_plan.W * kMaxBuckets) * sizeof(uint32_t));
             }
             if (split && rc == EK_OK && mask) {
                 // the split drops the masked-out lanes: whether one of them carried a non-finite x is found out here
@@ -1244,13 +1323,13 @@ int ek_hip_bucketed_pair_create_masked(int type, int index_type, int op, const v
                 sub->table_c = table_c ? (const float *) table_c + (size_t) sl * span : nullptr;
                 sub->correct_masked = false;
                 if (split) {
-                    // the slice's own elements, indices already local to the slice
-                    sub->n = cs.base[sl + 1] - cs.base[sl];
+                    // the slice's own elements (indices already local to the slice), as many as the device says -- n at most
+                    sub->n = n;
                     sub->win_lo = 0;
                     sub->win_span = (uint32_t) sub->table_size;
-                    if (sub->n == 0) { sub->empty_slice = true; continue; }
-                    rc = bucketed_create_paged<uint32_t>(sub, (const float *) cs.x + cs.base[sl], (const uint32_t *) cs.idx + cs.base[sl], all,
-                                                         bin_shift_of<float> - (want_half ? 1 : 0));
+                    const PagedSlice ps{ cs.range + 2 * sl, (uint32_t) sl * paged_slice_gap(pool_plan.W, pool_plan.page_shift), &pool_plan,
+                                         b, (uint32_t *) b->page_lists, (uint32_t *) pool_work.ptr, pool_pages };
+                    rc = bucketed_create_paged<uint32_t>(sub, (const float *) cs.x, (const uint32_t *) cs.idx, all, slice_shift, &ps);
                 } else {
                     sub->n = n;
                     sub->win_lo = (uint32_t) ((size_t) sl * span);
@@ -1287,9 +1366,8 @@ int ek_hip_bucketed_reduce(ek_hip_bucketed *b, int reduce_op, int map_op, void *
         Scratch partial;
         if (int rc = partial.alloc(b->slices.size() * sizeof(float))) return rc;
         SliceCounts counts{};
-        int S = 0;                                     // slices that hold elements
+        int S = 0;
         for (ek_hip_bucketed *sub : b->slices) {
-            if (sub->empty_slice) continue;
             if (int rc = bucketed_reduce<float>(sub, reduce_op, map_op, (float *) partial.ptr + S, keep_values != 0, keep_op)) return rc;
             counts.active[S++] = sub->active;
         }
@@ -1332,12 +1410,7 @@ int ek_hip_bucketed_scatter_add_scaled(ek_hip_bucketed *b, int count, void *cons
         for (size_t sl = 0; sl < b->slices.size(); ++sl) {
             void *sb[4];
             for (int s = 0; s < count; ++s) sb[s] = (float *) bases[s] + sl * b->slice_span;
-            if (b->slices[sl]->empty_slice) {          // nothing to add; a fresh table still has to hold zeros there
-                for (int s = 0; s < count; ++s)
-                    if (fresh && fresh[s])
-                        EK_HIP_CHECK(hipMemsetAsync(sb[s], 0, b->slices[sl]->table_size * sizeof(float), ctx().stream));
-                continue;
-            }
+            // (a slice that received no element has no pieces: the fold still writes a fresh table's zeros there)
             if (int rc = bucketed_scatter_add<float>(b->slices[sl], count, sb, from_u, map_ops, imm_bits, weighted, fresh, scale_bits)) return rc;
         }
         return EK_OK;

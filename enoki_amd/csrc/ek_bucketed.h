@@ -635,6 +635,7 @@ struct Bucketed {
     bool meta_clean_pending = false;       // finish() handed the counters to a launch that has not been checked yet (launched_reducing())
     uint32_t win_lo = 0, win_span = 0;     // a slice of a large table: only indices in [win_lo, win_lo + win_span) (ek_hip_bucketed::slices)
     bool correct_masked = true;            // the final reduction adds the masked-out lanes' map_op(0) terms (slices: their owner does)
+    Bucketed *owner = nullptr;             // a slice of a split table: pair_idx / x_b / u_b / m_b are the owner's page pool (not owned)
 
     bool has_mask = false;
     // (with or without a mask array: lanes whose index points outside the table are dropped by the partition too, and count like

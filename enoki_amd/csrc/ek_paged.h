@@ -75,6 +75,10 @@ template <typename T> struct PagedOut {
     uint32_t *class_stamp;     // [W] loop duration of every workgroup in 100 MHz ticks (nullptr: not recorded)
     uint32_t class_band;       // weights that all stay within this distance of 1 (Q16) count as equal
     uint32_t wdir_lds;         // != 0: the workgroup's wdir entries live in the LDS behind the records (>= slots words) instead of out.wdir
+                               // (DevRange: the number of entries that LDS holds; a workgroup with more slots uses out.wdir)
+    // (DevRange launches only: one slice of a split input, sized on the device -- see PagedSlice)
+    const uint32_t *range;     // device: [0] first element of the slice (a multiple of 4), [1] its element count
+    uint32_t range_page0;      // the slice's pages start at page (range[0] >> PS) + range_page0 of the pool
 #ifdef EK_PG_TIMING
     unsigned long long *dbg;   // [W][2][8] cycles per phase of waves 0 and 1 (measurement builds only)
 #endif
@@ -92,7 +96,12 @@ using PgV2 = __attribute__((ext_vector_type(2))) uint32_t;
 // IndexOnly (round 6): no value stream -- the pages carry the bucket-local INDEX as a 32-bit word (the value pages' slots), records of
 // 4 bytes (twice the buffer per bucket: 256 buckets keep 64-element pages), nothing is written to the 16-bit pages.  This is the
 // partition of an index array alone (ek_hip_index_partition_*: cfg4's pixel permutation): idx 4 read, 4 written per element.
-template <typename T, typename I, int PS, bool HasMask, bool IndexOnly = false>
+//
+// DevRange (sliced tables, PagedSlice): the input is slice out.range of a split -- its first element and its count are read from
+// the device on entry, workgroup w takes tiles [tiles w / W, tiles (w + 1) / W) of it, and its page slots start at a pool page that
+// follows from the same two numbers (paged_slice_pool), so that no host ever needs the slice's population.  `n`, `chunk` and
+// `slots` are the host's upper bounds (the LDS is sized by them).
+template <typename T, typename I, int PS, bool HasMask, bool IndexOnly = false, bool DevRange = false>
 __global__ __launch_bounds__(kPgThreads) void k_page_partition(PagedOut<T> out, const I *__restrict__ index, Arg<uint8_t> mask,
                                                                const T *__restrict__ x, size_t n, size_t chunk, int n_buckets,
                                                                int shift, uint32_t cap, uint32_t slots, int vec_ok) {
@@ -113,7 +122,21 @@ __global__ __launch_bounds__(kPgThreads) void k_page_partition(PagedOut<T> out, 
     const unsigned long long t_start = wall_clock64();
 #endif
     size_t begin = (size_t) w * chunk < n ? (size_t) w * chunk : n, end = begin + chunk < n ? begin + chunk : n;
-    if (out.class_w) {
+    size_t range_wbase = 0;
+    if constexpr (DevRange) {
+        const uint32_t first = out.range[0];
+        n = out.range[1];
+        index += first;
+        if constexpr (!IndexOnly) x += first;
+        if (mask.vec) mask.ptr += first;
+        const size_t tiles = (n + kPgTile - 1) / kPgTile, t0 = tiles * w / W, t1 = tiles * (w + 1) / W;
+        begin = t0 * kPgTile < n ? t0 * kPgTile : n;
+        end = t1 * kPgTile < n ? t1 * kPgTile : n;
+        range_wbase = ((size_t) first >> PS) + out.range_page0 + t0 * (kPgTile >> PS) + (size_t) w * n_buckets;
+        // (wdir_lds: how many directory entries the LDS behind the records holds -- this workgroup's slots, or global memory)
+        out.wdir_lds = (t1 - t0) * (kPgTile >> PS) + (size_t) n_buckets <= out.wdir_lds ? 1u : 0u;
+    }
+    if (!DevRange && out.class_w) {
         // the tiles of the whole input, dealt to the classes by weight and equally to a class's workgroups (W is a multiple of 8)
         const uint64_t NT = (n + kPgTile - 1) / kPgTile, per = W / kPgClasses, cls = w % kPgClasses, r = w / kPgClasses;
         uint64_t before = 0, mine = 0, all = 0;
@@ -134,7 +157,7 @@ __global__ __launch_bounds__(kPgThreads) void k_page_partition(PagedOut<T> out, 
             end = b1 < n ? (size_t) b1 : n;
         }
     }
-    const size_t wbase = (size_t) w * slots;                     // first page slot of this workgroup
+    const size_t wbase = DevRange ? range_wbase : (size_t) w * slots;     // first page slot of this workgroup
     const uint32_t lowmask = (1u << shift) - 1u, cap_pages = cap >> PS, cap_shift = 31u - (uint32_t) __builtin_clz(cap);
     const uint32_t spare = (uint32_t) n_buckets << cap_shift;         // one record behind the buffers
     // The workgroup's own page directory (slot -> sequence number << 8 | bucket) is written while pages are announced and read
@@ -553,6 +576,9 @@ constexpr int kPgDirSlices = 4;
 // The bucket's page list = the workgroups' lists one after the other (full pages), then the partially filled pages; bucket
 // bases of both lists; pieces for the consumers (as k_bin_scan_buckets: a share of `target_pieces` in proportion to the
 // bucket's population, at least one when it is not empty).  Grid: (bucket, slice of the bucket's list).
+// DevRange: the directory of one slice of a split input (k_page_partition<..., DevRange>): the workgroups' page slots and the
+// slice's place in the pool's full-page lists follow from range[0 .. 1] as in the partition; bases are pool positions.
+template <bool DevRange = false>
 static __global__ __launch_bounds__(256) void k_page_directory(uint32_t *__restrict__ glist_full, uint32_t *__restrict__ glist_part,
                                                                uint32_t *__restrict__ base_full, uint32_t *__restrict__ base_part,
                                                                uint32_t *__restrict__ piece_prefix,
@@ -561,11 +587,19 @@ static __global__ __launch_bounds__(256) void k_page_directory(uint32_t *__restr
                                                                const uint32_t *__restrict__ wlist, uint32_t W, uint32_t slots,
                                                                int n_buckets, uint32_t target_pieces,
                                                                uint32_t *__restrict__ class_w, const uint32_t *__restrict__ class_stamp,
-                                                               uint32_t class_band) {
+                                                               uint32_t class_band, const uint32_t *__restrict__ range,
+                                                               uint32_t range_page0, int page_shift) {
     __shared__ uint32_t wave_tot[4];
     __shared__ uint32_t row[1025], lrow[1024];
     __shared__ uint32_t s_fb, s_pb, s_f;
     const int t = threadIdx.x, b = blockIdx.x, slice = blockIdx.y;
+    uint32_t pool0 = 0;              // DevRange: first pool page of the slice
+    size_t range_tiles = 0;
+    if constexpr (DevRange) {
+        pool0 = (range[0] >> page_shift) + range_page0;
+        range_tiles = ((size_t) range[1] + kPgTile - 1) / kPgTile;
+        glist_full += pool0;
+    }
     // everything this workgroup reads from global memory, requested up front
     uint32_t f = 0, p = 0;
     if (t < n_buckets) {
@@ -592,8 +626,8 @@ static __global__ __launch_bounds__(256) void k_page_directory(uint32_t *__restr
     if (t == b) {
         s_fb = fi - f; s_pb = pi - p; s_f = f;
         if (slice == 0) {
-            base_full[b] = fi - f; base_part[b] = pi - p; piece_prefix[b] = qi - pieces;
-            if (b == n_buckets - 1) { base_full[n_buckets] = total_f; base_part[n_buckets] = total_p; piece_prefix[n_buckets] = total_q; }
+            base_full[b] = pool0 + fi - f; base_part[b] = pi - p; piece_prefix[b] = qi - pieces;
+            if (b == n_buckets - 1) { base_full[n_buckets] = pool0 + total_f; base_part[n_buckets] = total_p; piece_prefix[n_buckets] = total_q; }
         }
     }
     // row b of cnt_full: exclusive prefix over the workgroups (four per thread)
@@ -602,7 +636,11 @@ static __global__ __launch_bounds__(256) void k_page_directory(uint32_t *__restr
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const uint32_t wq = 4 * t + k;
-        if (wq < W) { row[wq] = run; lrow[wq] = (uint32_t) ((size_t) wq * slots) + lo[k]; }
+        if (wq < W) {
+            row[wq] = run;
+            lrow[wq] = (DevRange ? pool0 + (uint32_t) (range_tiles * wq / W * (kPgTile >> page_shift)) + wq * (uint32_t) n_buckets
+                                 : (uint32_t) ((size_t) wq * slots)) + lo[k];
+        }
         run += c[k];
     }
     if (t == 0) row[W] = total_c;
@@ -728,6 +766,14 @@ static inline PagedPlan paged_plan(size_t n, int n_buckets, int num_cu, bool wei
     p.page_slots = (size_t) p.W * p.slots;
     p.lds = ((size_t) n_buckets * p.cap + 2) * (index_only ? 4 : 8);
     return p;
+}
+
+/// The one page pool of a table split into S slices (k_page_partition<..., DevRange>): slice s's pages start at
+/// (range[0] >> PS) + s * paged_slice_gap() and end before the next slice's, whatever the populations are -- W workgroups hold at
+/// most (tiles of the slice) x kPgTile / 2^PS full pages plus one partially filled page per bucket each.
+static inline uint32_t paged_slice_gap(uint32_t W, int page_shift) { return W * (uint32_t) kMaxBuckets + (uint32_t) (kPgTile >> page_shift) + 2u; }
+static inline size_t paged_slice_pool_pages(size_t elements, int S, uint32_t W, int page_shift) {
+    return (elements >> page_shift) + 1 + (size_t) S * paged_slice_gap(W, page_shift);
 }
 
 } // namespace ek

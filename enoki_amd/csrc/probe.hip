@@ -535,7 +535,7 @@ extern "C" EK_API int ek_hip_probe_page_partition(int nts, int index64, const vo
     out.gtotal = meta;
     out.active = meta + kPgMetaBase;
     out.lo = 0; out.span = (uint32_t) std::min<size_t>(table_size, 0xFFFFFFFFu);
-    out.class_w = nullptr; out.class_stamp = nullptr; out.class_band = 0; out.wdir_lds = 0;             // (equal chunks: the probe measures the kernel, not the balancing)
+    out.class_w = nullptr; out.class_stamp = nullptr; out.class_band = 0; out.wdir_lds = 0; out.range = nullptr; out.range_page0 = 0;             // (equal chunks: the probe measures the kernel, not the balancing)
 #ifdef EK_PG_TIMING
     out.dbg = dbg;
 #else
@@ -566,10 +566,10 @@ extern "C" EK_API int ek_hip_probe_page_partition(int nts, int index64, const vo
 #undef EK_PP_LAUNCH
     EK_LAUNCH_CHECK("probe_page_partition", n, n * 14);
     if (directory) {
-        hipLaunchKernelGGL(k_page_directory, dim3(n_buckets, kPgDirSlices), dim3(256), 0, c.stream, glist_full, glist_part, base_full, base_part,
+        hipLaunchKernelGGL(k_page_directory<false>, dim3(n_buckets, kPgDirSlices), dim3(256), 0, c.stream, glist_full, glist_part, base_full, base_part,
                            piece_prefix, out.gtotal, (const uint32_t *) out.cnt_full, (const uint32_t *) out.loff,
                            (const uint32_t *) out.part, (const uint32_t *) wlist, p.W, p.slots, n_buckets, target_pieces,
-                           (uint32_t *) nullptr, (const uint32_t *) nullptr, 0u);
+                           (uint32_t *) nullptr, (const uint32_t *) nullptr, 0u, (const uint32_t *) nullptr, 0u, 0);
         EK_LAUNCH_CHECK("probe_page_directory", (size_t) n_buckets, 0);
     }
     return EK_OK;
