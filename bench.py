@@ -2,7 +2,7 @@
 """bench.py -- the north-star measurement: Gelem/s and %HBM-roofline of a 64 Mi-element DiffArray
 forward + backward() on MI355X (BASELINE.json: metric / configs[2]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3b|cfg3a|cfg2] [--n 67108864] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3b|cfg3a|cfg2] [--n 67108864] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic input that is already resident in HBM:
 
@@ -13,20 +13,23 @@ One "step" = one pass of the hot path over one batch of synthetic input that is 
   cfg3a a, b leaves of size N: y = hsum(sin(fmadd(a, x, b))); backward(y)
   cfg2  plain HIPArray: y = hsum(sin(exp(fmadd(a, x, b))))
 
-`value` is the headline workload (cfg3b unless --workload says otherwise).  On one GPU the other two GPU
-configurations of BASELINE.md section 4 are measured in the same run and reported under "also" (same timing
-method), because the three have separate pass lines.
+`value` is the headline workload (cfg3b unless --workload says otherwise).  A plain run measures nothing else: it sets
+up, warms up, times the K steps, writes --dump-outputs and prints the line.  Everything else the benchmark measures or
+checks comes with --full (the sub-records below; `roofline`, `cpu_baseline`, `parity`, `also` and `weak` are null
+without it).  With --full on one GPU the other two GPU configurations of BASELINE.md section 4 are measured in the
+same run and reported under "also" (same timing method), because the three have separate pass lines.
 
 Multi-GPU (one process per GPU; `python bench.py --gpus N` starts its own ranks): the arrays are index-range
 sharded, the K-element tables are replicated; per step ONE asynchronous RCCL all-reduce finishes y and the table
 gradients (enoki_amd/dist.py).  Default --scaling strong -- what BASELINE.json's metric, `north_star` and BASELINE.md
-section 4 state: --n (64 Mi) elements IN TOTAL, --n / N per GPU; `value` = --n / max-over-ranks time.  The same run then
-also measures the weak form (every GPU owns --n elements of an array of N x --n) and carries it as the labelled
-sub-record `weak` of the same line (--no-weak skips it; --scaling weak makes it the `value` as in round 5).
+section 4 state: --n (64 Mi) elements IN TOTAL, --n / N per GPU; `value` = --n / max-over-ranks time.  With --full the
+same run then also measures the weak form (every GPU owns --n elements of an array of N x --n) and carries it as the
+labelled sub-record `weak` of the same line (--no-weak skips it; --scaling weak makes it the `value` as in round 5).
 
-The JSON line carries, besides the contract fields, `roofline` for the dominant kernel (live per-launch timing
-with HIP events on the library stream, ek_hip_profile_*) and `cpu_baseline` (the reference build oracle/_ref, or
-the C restatement when it is absent, timed on ONE host core -- the reference has no threading).
+With --full the JSON line carries, besides the contract fields, `roofline` for the dominant kernel (live per-launch
+timing with HIP events on the library stream, ek_hip_profile_*) and `cpu_baseline` (the reference build oracle/_ref, or
+the C restatement when it is absent, timed on ONE host core -- the reference has no threading) with `parity`, the
+timed step's outputs against it.
 """
 import argparse
 import json
@@ -104,14 +107,19 @@ def parse():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="cfg3b", choices=["cfg3b", "cfg3a", "cfg2", "cfg4", "cfg4_packed", "cfg4_unfused", "cfg4_bucketed", "cfg5", "cfg5_unfused", "cfg5_cpp"] + list(CFG3B_VARIANTS))
     ap.add_argument("--n", type=int, default=1 << 26, help="elements IN TOTAL (--scaling strong, the default: what BASELINE.md section 4 and north_star state) or per GPU (--scaling weak)")
-    ap.add_argument("--no-weak", action="store_true", help="N > 1 GPUs: skip the weak-scaling sub-record (`weak` in the line)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the secondary workloads (`also`), the CPU "
+                         "baseline and the parity of the timed step against it, the per-kernel timing and roofline of the headline "
+                         "step, and on N > 1 GPUs the weak-scaling sub-record.  Off by default: a plain run sets up, warms up, times "
+                         "the steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--no-weak", action="store_true", help="--full on N > 1 GPUs: skip the weak-scaling sub-record (`weak` in the line)")
     ap.add_argument("--scaling", default="strong", choices=["weak", "strong"],
                     help="cfg2 / cfg3a / cfg3b on N > 1 GPUs.  strong (default, the contract's configuration): --n elements in total, "
                          "--n / N per GPU; weak: every GPU owns an index range of --n elements of an array of N x --n "
-                         "(DESIGN.md section 7 for what each can give).  With strong, the weak measurement rides along as `weak`.")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the secondary workloads on one GPU")
-    ap.add_argument("--profile-steps", type=int, default=5)
+                         "(DESIGN.md section 7 for what each can give).  With strong and --full, the weak measurement rides along as `weak`.")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity check")
+    ap.add_argument("--no-also", action="store_true", help="--full: skip the secondary workloads on one GPU")
+    ap.add_argument("--profile-steps", type=int, default=5, help="--full: steps timed kernel by kernel for `roofline`")
     ap.add_argument("--deterministic", action="store_true", help="bit-reproducible fp scatter_add (sorted path)")
     ap.add_argument("--eager", action="store_true", help="(default since round 4; kept for old command lines)")
     ap.add_argument("--dump-gradients", default=None, metavar="DIR", help="cfg3b: every rank saves what it holds of the table gradients after the exchange (owned slices when reduce-scattered) as DIR/grad_rank<r>.npz -- for the multi-rank parity tests")
@@ -659,56 +667,57 @@ class Bench:
         if self.args.dump_outputs and workload == self.args.workload:
             dumped = caller_outputs(out)
         gelem_s = units / (ms_per_step * 1e-3) / 1e9
-        # per-kernel timing of the same step (run eagerly): one HIP event per launch on the library stream
-        torch.cuda.synchronize()
-        t_prof = time.perf_counter()
-        ek.hip_profile_begin()
-        for _ in range(profile_steps):
-            step()
-        prof = json.loads(ek.hip_profile_end())
-        if packer:
-            packer.wait_all()
-        torch.cuda.synchronize()
-        profiled_ms_per_step = (time.perf_counter() - t_prof) / max(profile_steps, 1) * 1e3     # (the steps the event deltas below decompose)
-        kernels = []
-        for k in prof:
-            if k["launches"] == 0 or k["elements"] // k["launches"] < 1024:
-                continue        # scalar bookkeeping launches (size-1 arrays) are not bandwidth kernels
-            avg_ms = k["total_ms"] / k["launches"]
-            bpl = k["bytes"] / k["launches"]
-            kernels.append({"kernel": k["kernel"], "launches_per_step": k["launches"] / profile_steps,
-                            "avg_ms": round(avg_ms, 5), "bytes_per_launch": int(bpl),
-                            "tb_s": round(bpl / avg_ms / 1e9, 4) if avg_ms > 0 else None,
-                            "share_ms_per_step": round(k["total_ms"] / profile_steps, 5)})
-        kernels.sort(key=lambda k: -k["share_ms_per_step"])
-        total_bytes_step = sum(k["bytes"] for k in prof) / profile_steps
         roofline = None
-        if kernels:
-            dom = kernels[0]
-            achieved = dom["bytes_per_launch"] / dom["avg_ms"] / 1e6      # GB/s
-            whole = total_bytes_step / (ms_per_step * 1e-3) / 1e9
-            traffic, traffic_source = pmc_traffic(dom["kernel"]) if self.n == (1 << 26) else (None, "PMC summaries are taken at 64 Mi elements per GPU")
-            rp_us, rp_src = rocprof_avg_us(dom["kernel"]) if self.n == (1 << 26) else (None, "kernel-trace summaries are taken at 64 Mi elements per GPU")
-            frac_live = achieved / (HBM_PEAK_TBS * 1000)
-            frac_rocprof = dom["bytes_per_launch"] / (rp_us * 1e-6) / 1e9 / (HBM_PEAK_TBS * 1000) if rp_us else None
-            # frac: the PROFILE-derived figure -- the algorithmic bytes of a launch over the kernel's average duration in the committed
-            # rocprofv3 kernel trace of THIS tree (no gaps; only when the trace's kernels_sha16 stamp equals this tree's) -- and the live
-            # one otherwise; frac_live: from the HIP-event deltas of this run (a delta includes the gap to the previous launch)
-            frac = frac_rocprof if frac_rocprof else frac_live
-            if frac_rocprof:
-                achieved = dom["bytes_per_launch"] / (rp_us * 1e-6) / 1e9
-            roofline = {"bound": "hbm", "kernel": dom["kernel"], "achieved": round(achieved, 1),
-                        "peak": HBM_PEAK_TBS * 1000, "unit": "GB/s", "frac": round(frac, 4),
-                        "frac_source": "rocprofv3 kernel trace of this tree (" + KSTATS_FILE + ")" if frac_rocprof else "live HIP-event deltas (no stamped trace of this tree)",
-                        "frac_live": round(frac_live, 4), "frac_rocprof": round(frac_rocprof, 4) if frac_rocprof else None,
-                        "rocprof_avg_us": rp_us, "rocprof_source": rp_src,
-                        "traffic": traffic, "traffic_source": traffic_source,
-                        "whole_step": {"algorithmic_bytes": int(total_bytes_step),
-                                       "bytes_per_elt": round(total_bytes_step / max(N_RAYS_PER_GPU if workload.startswith("cfg4") else N_PATHS_PER_GPU if workload.startswith("cfg5") else self.n, 1), 2),
-                                       "achieved_GBs": round(whole, 1), "frac": round(whole / (HBM_PEAK_TBS * 1000), 4)},
-                        "kernels": kernels}
-        if roofline and workload == self.args.workload:
-            roofline["measured_stream_ceiling"] = self.stream_ceiling()
+        if profile_steps > 0:
+            # (--full) per-kernel timing of the same step (run eagerly): one HIP event per launch on the library stream
+            torch.cuda.synchronize()
+            t_prof = time.perf_counter()
+            ek.hip_profile_begin()
+            for _ in range(profile_steps):
+                step()
+            prof = json.loads(ek.hip_profile_end())
+            if packer:
+                packer.wait_all()
+            torch.cuda.synchronize()
+            profiled_ms_per_step = (time.perf_counter() - t_prof) / profile_steps * 1e3     # (the steps the event deltas below decompose)
+            kernels = []
+            for k in prof:
+                if k["launches"] == 0 or k["elements"] // k["launches"] < 1024:
+                    continue        # scalar bookkeeping launches (size-1 arrays) are not bandwidth kernels
+                avg_ms = k["total_ms"] / k["launches"]
+                bpl = k["bytes"] / k["launches"]
+                kernels.append({"kernel": k["kernel"], "launches_per_step": k["launches"] / profile_steps,
+                                "avg_ms": round(avg_ms, 5), "bytes_per_launch": int(bpl),
+                                "tb_s": round(bpl / avg_ms / 1e9, 4) if avg_ms > 0 else None,
+                                "share_ms_per_step": round(k["total_ms"] / profile_steps, 5)})
+            kernels.sort(key=lambda k: -k["share_ms_per_step"])
+            total_bytes_step = sum(k["bytes"] for k in prof) / profile_steps
+            if kernels:
+                dom = kernels[0]
+                achieved = dom["bytes_per_launch"] / dom["avg_ms"] / 1e6      # GB/s
+                whole = total_bytes_step / (ms_per_step * 1e-3) / 1e9
+                traffic, traffic_source = pmc_traffic(dom["kernel"]) if self.n == (1 << 26) else (None, "PMC summaries are taken at 64 Mi elements per GPU")
+                rp_us, rp_src = rocprof_avg_us(dom["kernel"]) if self.n == (1 << 26) else (None, "kernel-trace summaries are taken at 64 Mi elements per GPU")
+                frac_live = achieved / (HBM_PEAK_TBS * 1000)
+                frac_rocprof = dom["bytes_per_launch"] / (rp_us * 1e-6) / 1e9 / (HBM_PEAK_TBS * 1000) if rp_us else None
+                # frac: the PROFILE-derived figure -- the algorithmic bytes of a launch over the kernel's average duration in the committed
+                # rocprofv3 kernel trace of THIS tree (no gaps; only when the trace's kernels_sha16 stamp equals this tree's) -- and the live
+                # one otherwise; frac_live: from the HIP-event deltas of this run (a delta includes the gap to the previous launch)
+                frac = frac_rocprof if frac_rocprof else frac_live
+                if frac_rocprof:
+                    achieved = dom["bytes_per_launch"] / (rp_us * 1e-6) / 1e9
+                roofline = {"bound": "hbm", "kernel": dom["kernel"], "achieved": round(achieved, 1),
+                            "peak": HBM_PEAK_TBS * 1000, "unit": "GB/s", "frac": round(frac, 4),
+                            "frac_source": "rocprofv3 kernel trace of this tree (" + KSTATS_FILE + ")" if frac_rocprof else "live HIP-event deltas (no stamped trace of this tree)",
+                            "frac_live": round(frac_live, 4), "frac_rocprof": round(frac_rocprof, 4) if frac_rocprof else None,
+                            "rocprof_avg_us": rp_us, "rocprof_source": rp_src,
+                            "traffic": traffic, "traffic_source": traffic_source,
+                            "whole_step": {"algorithmic_bytes": int(total_bytes_step),
+                                           "bytes_per_elt": round(total_bytes_step / max(N_RAYS_PER_GPU if workload.startswith("cfg4") else N_PATHS_PER_GPU if workload.startswith("cfg5") else self.n, 1), 2),
+                                           "achieved_GBs": round(whole, 1), "frac": round(whole / (HBM_PEAK_TBS * 1000), 4)},
+                            "kernels": kernels}
+            if roofline and workload == self.args.workload:
+                roofline["measured_stream_ceiling"] = self.stream_ceiling()
         y_val = float(out["y"].numpy()[0])
         if packer and out.get("reduced"):
             y_val = float(out["reduced"][0].item())
@@ -724,7 +733,9 @@ class Bench:
                          begin=0, end=K_TABLE)
         if dumped is not None:
             write_outputs(self.args.dump_outputs, dumped)
-        outputs = {k: out[k].numpy() for k in ("gA", "gB", "ga", "gb") if k in out} if self.world == 1 and workload == self.args.workload else {}
+        # (--full) the timed step's gradients, for the parity check against the CPU baseline
+        outputs = {k: out[k].numpy() for k in ("gA", "gB", "ga", "gb") if k in out} \
+            if self.args.full and self.world == 1 and workload == self.args.workload else {}
         outputs["y"] = y_val
         if roofline:
             # the per-kernel times and the step they are said to add up to, taken in the SAME state of the device: kernels on
@@ -962,12 +973,14 @@ def main():
         import faulthandler
         faulthandler.dump_traceback_later(900, exit=True)
     b = Bench(args)
-    main_res = b.run(args.workload, args.steps, args.warmup, args.profile_steps, pre_warm_s=args.pre_warm_s)
+    # a plain run stops at the headline figure; everything below that it skips (profiled steps, weak sub-record, secondary
+    # workloads, CPU baseline and parity) is --full
+    main_res = b.run(args.workload, args.steps, args.warmup, args.profile_steps if args.full else 0, pre_warm_s=args.pre_warm_s)
     pre_warm_s = b.pre_warm_s
     # N > 1 under the contract's (strong) mode: the weak measurement of the SAME run as a labelled sub-record -- every rank takes
     # part (collectives), rank 0 reports
     weak = None
-    if b.world > 1 and not b.weak and not args.no_weak:
+    if args.full and b.world > 1 and not b.weak and not args.no_weak:
         bw = Bench(args, scaling="weak")
         bw.side_record = True               # (no gradient dump: --dump-gradients is about the record's problem)
         rw = bw.run(args.workload, args.steps, args.warmup, 1, pre_warm_s=min(args.pre_warm_s, 0.3))
@@ -976,7 +989,7 @@ def main():
                 "note": "every GPU owns --n elements of an array of N x --n; all elements of all ranks / max-over-ranks time; same kernels, same exchange"}
         del bw
     also = {}
-    if b.world == 1 and not args.no_also:
+    if args.full and b.world == 1 and not args.no_also:
         for w in ("cfg3a", "cfg2", "cfg3b") + tuple(CFG3B_VARIANTS) + ("cfg4_bucketed", "cfg4", "cfg4_packed", "cfg4_unfused", "cfg5", "cfg5_unfused"):
             if w != args.workload:
                 r = b.run(w, args.steps // 2, 2, 3, max_seconds=1.0)
@@ -993,7 +1006,7 @@ def main():
                     also[w]["parity"] = ("against examples/path_trace.h instantiated on the reference's arrays (oracle/_ref: ref_cfg5), 1 Mi paths, "
                                          "loss and texture gradient inside the class-D bounds: tests/test_cfg5_gpu.py")
     cpu, parity = None, None
-    if b.rank == 0 and b.world == 1 and not args.no_cpu_baseline:
+    if args.full and b.rank == 0 and b.world == 1 and not args.no_cpu_baseline:
         cpu, ref_out = cpu_baseline(args.workload, b.N)
         if ref_out and args.workload in ("cfg3b", "cfg3a", "cfg2"):
             parity = check_parity(args.workload, b.N, main_res["outputs"], ref_out, cpu["kind"])
@@ -1002,7 +1015,7 @@ def main():
     if b.rank == 0:
         line = {
             "metric": "Gelem/s + %HBM-roofline, 64M-elt DiffArray backward(), 1/2/4/8 MI355X",
-            "value": main_res["value"], "unit": "Gelem/s", "n_gpus": b.world, "steps": args.steps, "warmup": args.warmup,
+            "value": main_res["value"], "unit": "Gelem/s", "n_gpus": b.world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": main_res["ms_per_step"], "pre_warm_s": pre_warm_s, "value_source": "eager", "eager_ms_per_step": main_res["eager_ms_per_step"],
             "graph_ms_per_step": main_res["graph_ms_per_step"], "higher_is_better": True,
             "scaling": "weak" if b.weak else "strong", "vs_baseline": None,

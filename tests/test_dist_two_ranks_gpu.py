@@ -56,10 +56,10 @@ def test_two_ranks_match_one(workload, tmp_path):
 
 def test_default_is_the_contracts_strong_scaling_with_the_weak_result_alongside():
     """`python bench.py --gpus 2` without further options measures what BASELINE.md section 4 / north_star state -- --n elements IN
-    TOTAL, n / 2 per rank, `"scaling": "strong"` -- and carries the weak measurement of the same run (every rank owns --n elements of
-    an array of 2 x --n) as the labelled sub-record `weak`; `--scaling weak` makes that the `value` (round 5's default)"""
+    TOTAL, n / 2 per rank, `"scaling": "strong"` -- and with --full carries the weak measurement of the same run (every rank owns --n
+    elements of an array of 2 x --n) as the labelled sub-record `weak`; `--scaling weak` makes that the `value` (round 5's default)"""
     n = 1 << 21
-    two = run_bench("cfg3b", n, 2, 0)
+    two = run_bench("cfg3b", n, 2, 0, extra=["--full"])
     assert two["scaling"] == "strong" and two["config"]["elements_per_gpu"] == n // 2 and two["config"]["elements_total"] == n
     assert two["config"]["collectives_per_step"] == 1
     truth, bound = truth_y("cfg3b", n)

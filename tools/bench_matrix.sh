@@ -1,5 +1,5 @@
 # every bench.py entry point once, small and quick: catches flag combinations that break (GPU box: bash tools/bench_matrix.sh)
-run() { echo "== $*"; timeout 300 python bench.py --no-cpu-baseline --no-also --steps 3 --warmup 1 --profile-steps 1 "$@" 2>&1 | grep "^{\"metric\|Error\|error" | python -c "
+run() { echo "== $*"; timeout 300 python bench.py --full --no-cpu-baseline --no-also --steps 3 --warmup 1 --profile-steps 1 "$@" 2>&1 | grep "^{\"metric\|Error\|error" | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

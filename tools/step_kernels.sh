@@ -1,5 +1,5 @@
 # per-kernel breakdown of the headline step (HIP events per launch, eager repeat inside bench.py)
-python bench.py --no-cpu-baseline --no-also --steps 20 --warmup 3 --profile-steps 5 "$@" | python -c "
+python bench.py --full --no-cpu-baseline --no-also --steps 20 --warmup 3 --profile-steps 5 "$@" | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(d['value'], d['unit'], d['ms_per_step'], 'ms/step', d['config'].get('step_replay'))
