@@ -439,6 +439,7 @@ Bucketed::~Bucketed() {
         r.clean[meta_slot] = meta_clean;
         meta = nullptr;
     }
+    if (meta_borrowed) meta = nullptr;
     for (void *p : { meta, early, page_lists })
         if (p) ek_hip_free(p);
     if (!owner)
@@ -521,6 +522,7 @@ static int bucketed_create(Bucketed *b, const T *x, const I *index) {
 struct CoarseSplit {
     void *idx = nullptr, *x = nullptr, *meta = nullptr;      // slice-local indices and x in slice order; counts / bases / ranges
     uint32_t *range = nullptr;                               // device: [S][2] first element, element count
+    uint32_t *share = nullptr;                               // device: [S] the slice's share of a piece budget (coarse_split(.., budget))
     size_t elements = 0;                                     // what idx / x hold, the alignment gaps included
     ~CoarseSplit() {
         for (void *p : { idx, x, meta })
@@ -529,22 +531,35 @@ struct CoarseSplit {
 };
 
 // the runs of the split: slice s from a multiple of 4 elements on (bucket_base: where k_bin_partition places them)
+// share (optional): `budget` pieces dealt to the slices by population, rounded up -- their sum stays within budget + S
 static __global__ __launch_bounds__(64) void k_slice_ranges(uint32_t *__restrict__ range, uint32_t *__restrict__ bucket_base,
-                                                             const uint32_t *__restrict__ row_total, int S) {
+                                                             const uint32_t *__restrict__ row_total, int S,
+                                                             uint32_t *__restrict__ share, uint32_t budget) {
     if (threadIdx.x != 0) return;
     uint32_t first = 0;
+    uint64_t kept = 0;
     for (int s = 0; s < S; ++s) {
         const uint32_t cnt = row_total[s];
         bucket_base[s] = first;
         range[2 * s] = first;
         range[2 * s + 1] = cnt;
         first += (cnt + 3u) & ~3u;
+        kept += cnt;
     }
     bucket_base[S] = first;
+    if (share)
+        for (int s = 0; s < S; ++s) {
+            const uint64_t part = kept ? ((uint64_t) row_total[s] * budget + kept - 1) / kept : 0u;
+            share[s] = part ? (uint32_t) part : 1u;
+        }
 }
 
+constexpr int kMaxSlices = 64;
+
+/// `budget` != 0 (scatter_add_sliced): cs.share[s] = the slice's share of that many pieces, and the launches carry scatter_add's names
 template <int Shift>
-static int coarse_split(CoarseSplit &cs, const float *x, const uint32_t *index, const Arg<uint8_t> &mask, size_t n, int S) {
+static int coarse_split(CoarseSplit &cs, const float *x, const uint32_t *index, const Arg<uint8_t> &mask, size_t n, int S,
+                        uint32_t budget = 0) {
     RoctxRange range("enoki-hip: slice partition");
     Context &c = ctx();
     unsigned blocks = (unsigned) std::min<size_t>((size_t) c.num_cu * 4, (n + kTile - 1) / kTile);
@@ -561,13 +576,15 @@ static int coarse_split(CoarseSplit &cs, const float *x, const uint32_t *index, 
     if (int rc = ek_hip_malloc(cs.elements * sizeof(uint32_t), &cs.idx)) return rc;
     if (int rc = ek_hip_malloc(cs.elements * sizeof(float), &cs.x)) return rc;
     uint32_t *counts = (uint32_t *) cs.meta, *row_total = counts + count_entries, *bucket_base = row_total + kMaxBuckets;
-    cs.range = bucket_base + kMaxBuckets + 2;
+    cs.range = bucket_base + kMaxBuckets + 2;                // [2 kMaxSlices], then share[kMaxSlices]
+    cs.share = budget ? cs.range + 2 * kMaxSlices : nullptr;
     hipLaunchKernelGGL((k_bin_count<uint32_t, Shift>), dim3(blocks), dim3(kThreads), 0, c.stream, counts, index, mask, n, chunk, S,
                        rep_shift, vec_ok);
-    EK_LAUNCH_CHECK("bucket_slice_count", n, n * sizeof(uint32_t) + arg_bytes(mask, n));
+    EK_LAUNCH_CHECK(budget ? "scatter_add_slice_count" : "bucket_slice_count", n, n * sizeof(uint32_t) + arg_bytes(mask, n));
     hipLaunchKernelGGL(k_bin_scan_rows, dim3(S), dim3(1024), 0, c.stream, counts, row_total, blocks);
-    hipLaunchKernelGGL(k_slice_ranges, dim3(1), dim3(64), 0, c.stream, cs.range, bucket_base, (const uint32_t *) row_total, S);
-    EK_LAUNCH_CHECK("bucket_slice_scan", count_entries, 2 * count_entries * sizeof(uint32_t));
+    hipLaunchKernelGGL(k_slice_ranges, dim3(1), dim3(64), 0, c.stream, cs.range, bucket_base, (const uint32_t *) row_total, S, cs.share,
+                       budget);
+    EK_LAUNCH_CHECK(budget ? "scatter_add_slice_scan" : "bucket_slice_scan", count_entries, 2 * count_entries * sizeof(uint32_t));
     BinStreams<float, 1> st;
     st.value[0] = Arg<float>{ x, 0.f, 1u };
     st.weight[0] = Arg<float>{ nullptr, 1.f, 0u };
@@ -577,7 +594,7 @@ static int coarse_split(CoarseSplit &cs, const float *x, const uint32_t *index, 
     hipLaunchKernelGGL((k_bin_partition<float, uint32_t, Shift, uint32_t, 1>), dim3(blocks), dim3(kThreads), 0, c.stream,
                        (uint32_t *) cs.idx, st, (const uint32_t *) counts, (const uint32_t *) bucket_base, index, mask, n, chunk, S, 0,
                        vec_ok);
-    EK_LAUNCH_CHECK("bucket_slice_partition", n, n * 16 + arg_bytes(mask, n));
+    EK_LAUNCH_CHECK(budget ? "scatter_add_slice_partition" : "bucket_slice_partition", n, n * 16 + arg_bytes(mask, n));
     return EK_OK;
 }
 
@@ -592,6 +609,11 @@ struct PagedSlice {
     uint32_t *glist_full;          // the pool's full-page lists
     uint32_t *work;                // wdir | wlist (pool pages each) | cnt_full | loff | part ([kMaxBuckets][W] each)
     size_t pool_pages;
+    // scatter_add_sliced: the slices' counter blocks and glist_part lists are parts of ONE allocation each, a fixed stride apart and
+    // zeroed by one fill, so that ONE launch finds every slice's lists (SliceLists); the piece budget is shared out on the device
+    void *meta = nullptr;                   // the slice's counter block (counters zeroed by the caller)
+    uint32_t *glist_part = nullptr;
+    const uint32_t *piece_share = nullptr;  // device: [0] pieces this slice may have (nullptr: the host's target for every slice)
 };
 
 /// The same object from the single-pass paged partition (ek_paged.h): 4-byte element types, n <= 2^30.  One streaming pass
@@ -615,7 +637,11 @@ static int bucketed_create_paged(Bucketed *b, const float *x, const I *index, co
     // the counter block: one of the context's ring when one is free (then usually without a fill, see MetaRing), else an allocation
     bool filled = false;
     static const bool use_ring = [] { const char *e = getenv("ENOKI_HIP_META_RING"); return !e || atoi(e) != 0; }();
-    if (use_ring && b->max_pieces <= MetaRing::kPartials && refuse_while_capturing_quiet() == EK_OK) {
+    if (slice && slice->meta) {
+        b->meta = slice->meta;
+        b->meta_borrowed = true;
+        filled = true;
+    } else if (use_ring && b->max_pieces <= MetaRing::kPartials && refuse_while_capturing_quiet() == EK_OK) {
         MetaRing &r = meta_ring();
         for (int k = 0; k < MetaRing::kBlocks && b->meta_slot < 0; ++k) {
             if (r.busy[k]) continue;
@@ -629,16 +655,17 @@ static int bucketed_create_paged(Bucketed *b, const float *x, const I *index, co
             filled = r.clean[k];
         }
     }
-    if (b->meta_slot < 0)
+    if (b->meta_slot < 0 && !b->meta_borrowed)
         if (int rc = ek_hip_malloc(meta_words * sizeof(uint32_t) + (size_t) b->max_pieces * 16 + 16, &b->meta)) return rc;
     const size_t part_entries = (size_t) p.W * n_buckets;
     if (slice) {
         b->owner = slice->owner;
         b->pair_idx = slice->owner->pair_idx;
         b->x_b = slice->owner->x_b;
-        if (int rc = ek_hip_malloc((part_entries + 1) * sizeof(uint32_t), &b->page_lists)) return rc;
+        if (!slice->glist_part)
+            if (int rc = ek_hip_malloc((part_entries + 1) * sizeof(uint32_t), &b->page_lists)) return rc;
         b->glist_full = slice->glist_full;
-        b->glist_part = (uint32_t *) b->page_lists;
+        b->glist_part = slice->glist_part ? slice->glist_part : (uint32_t *) b->page_lists;
     } else {
         if (int rc = ek_hip_malloc(b->positions * sizeof(uint16_t), &b->pair_idx)) return rc;
         if (int rc = ek_hip_malloc(b->positions * sizeof(float), &b->x_b)) return rc;
@@ -723,7 +750,7 @@ static int bucketed_create_paged(Bucketed *b, const float *x, const I *index, co
         hipLaunchKernelGGL(k_page_directory<true>, dim3(n_buckets, kPgDirSlices), dim3(256), 0, c.stream, b->glist_full, b->glist_part, b->bucket_base,
                            b->base_part, b->piece_prefix, gtotal, (const uint32_t *) out.cnt_full,
                            (const uint32_t *) out.loff, (const uint32_t *) out.part, (const uint32_t *) out.wlist, p.W, p.slots, n_buckets,
-                           target_pieces, (uint32_t *) nullptr, (const uint32_t *) nullptr, band, slice->range, slice->page0, p.page_shift);
+                           target_pieces, (uint32_t *) nullptr, slice->piece_share, band, slice->range, slice->page0, p.page_shift);
     else
     hipLaunchKernelGGL(k_page_directory<false>, dim3(n_buckets, kPgDirSlices), dim3(256), 0, c.stream, b->glist_full, b->glist_part, b->bucket_base,
                        b->base_part, b->piece_prefix, gtotal, (const uint32_t *) out.cnt_full,
@@ -1072,6 +1099,174 @@ bool scatter_add_paged_applicable(size_t table_size, size_t n) {
            table_size >= (size_t) 32 * bins_of<float> && table_size <= (size_t) kMaxBuckets * bins_of<float>;
 }
 
+// ---- scatter_add(value, index, mask) into a table beyond 256 buckets, sized on the device ----------------------------------------
+// The adjoint of every gather from a large table that is not in the bucket-ordered menu, and a plain scatter_add from user code.
+// (index, value) are split by slice of 256 buckets (coarse_split: masked-out pairs and indices beyond the last slice are dropped
+// there), every slice partitions its own run into ONE page pool (k_page_partition<.., DevRange> + k_page_directory<true>, its size
+// read from range[s] on entry), then ONE launch adds the pairs of all slices' pieces in the LDS and ONE launch folds the per-piece
+// tables into base + s * span.  Nothing is read back and the host decides nothing from the index values: the call can be part of a
+// captured step graph, and every replay follows the slice populations it finds.  An empty slice has no pieces, its fold adds nothing.
+//
+// The two launches over all slices number the pieces FLAT: slice s owns pieces [P_s, P_s + q_s), q_s = the last entry of its piece
+// prefix, P_s the sum of those of the slices before it -- S <= 64 words that one wave of every workgroup reads and scans.  A piece's
+// workgroup then finds its bucket and its pages in slice s's lists, which lie a fixed stride apart (SliceLists: 48 bytes of kernel
+// arguments whatever S is; no descriptor table to copy to the device).  The piece budget of one unsliced call is dealt to the slices
+// by population on the device (k_slice_ranges), so the partial tables of all slices together are `budget + S + one per bucket`.
+struct SliceLists {
+    const uint32_t *meta;          // S counter blocks, meta_stride words apart: counters | base_full[257] | base_part[257] | piece_prefix[257]
+    const uint32_t *glist_full;    // the pool's full-page list (the slices' bases are pool positions)
+    const uint32_t *glist_part;    // S lists, part_stride entries apart
+    uint32_t meta_stride, part_stride;
+    size_t table_size;
+    int S, shift;
+};
+constexpr uint32_t kSliceBaseFull = kPgCounterWords, kSliceBasePart = kSliceBaseFull + kMaxBuckets + 1,
+                   kSlicePiecePrefix = kSliceBasePart + kMaxBuckets + 1;
+
+__device__ __forceinline__ int slice_buckets(const SliceLists &sl, int s) {
+    const size_t span = (size_t) kMaxBuckets << sl.shift, left = sl.table_size - (size_t) s * span;
+    return (int) (((left < span ? left : span) + ((size_t) 1 << sl.shift) - 1) >> sl.shift);
+}
+/// lane s < S of the calling wave: pieces of slice s in `count`, and of slices 0 .. s in the result
+__device__ __forceinline__ uint32_t slice_piece_scan(const SliceLists &sl, int s, uint32_t &count) {
+    count = s < sl.S ? sl.meta[(size_t) s * sl.meta_stride + kSlicePiecePrefix + slice_buckets(sl, s)] : 0u;
+    uint32_t incl = count;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d, 64);
+        if (s >= d) incl += up;
+    }
+    return incl;
+}
+__device__ __forceinline__ BucketLists slice_lists(const SliceLists &sl, int s) {
+    const uint32_t *m = sl.meta + (size_t) s * sl.meta_stride;
+    return BucketLists{ m + kSliceBaseFull, m + kSlicePiecePrefix, m + kSliceBasePart, sl.glist_full,
+                        sl.glist_part + (size_t) s * sl.part_stride, slice_buckets(sl, s) };
+}
+
+/// grid: the bound on the pieces of all slices together; a workgroup beyond the pieces that exist leaves at once
+template <int V>
+__global__ __launch_bounds__(kBucketThreads) void k_bucket_accumulate_slices(float *__restrict__ partials,
+                                                                             const uint16_t *__restrict__ pair_idx,
+                                                                             const float *__restrict__ x_b, SliceLists sl) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    float *acc = reinterpret_cast<float *>(lds_raw);
+    __shared__ uint32_t s_slice[3];                 // the slice of piece blockIdx.x, its first piece, pieces of all slices
+    const int Bins = 1 << sl.shift;
+    if (threadIdx.x < 64) {
+        uint32_t count;
+        const uint32_t incl = slice_piece_scan(sl, (int) threadIdx.x, count);
+        if (incl - count <= blockIdx.x && blockIdx.x < incl) { s_slice[0] = threadIdx.x; s_slice[1] = incl - count; }
+        if (threadIdx.x == 63) s_slice[2] = incl;
+    }
+    __syncthreads();
+    if (blockIdx.x >= s_slice[2]) return;
+    const BucketLists bl = slice_lists(sl, (int) s_slice[0]);
+    int bucket;
+    PieceRange range;
+    if (!bucket_piece_at<5>(bl, blockIdx.x - s_slice[1], bucket, range)) return;
+    for (int j = threadIdx.x; j < Bins; j += kBucketThreads) acc[j] = 0.f;
+    __syncthreads();
+    AccumulateBody<float, 1, V, EK_COPY, 2> body{};
+    body.acc = acc; body.pair_idx = pair_idx; body.u_b = nullptr; body.x_b = x_b; body.Bins = Bins;
+    body.need_u = false; body.need_x = true;
+    walk_piece<5, V>(bl, range, body);
+    __syncthreads();
+    float *out = partials + (size_t) blockIdx.x * Bins;
+    for (int j = threadIdx.x; j < Bins; j += kBucketThreads) out[j] = acc[j];
+}
+
+/// target[k] += the partial tables of the pieces of k's bucket; a workgroup covers 1024 consecutive entries: one bucket of one slice
+__global__ __launch_bounds__(256) void k_bin_fold_slices(float *__restrict__ target, const float *__restrict__ partials, SliceLists sl) {
+    __shared__ uint32_t s_first;                    // first piece of this workgroup's slice
+    const size_t kb = (size_t) blockIdx.x * 256 * kFoldPerLane;
+    const int s = (int) (kb >> (sl.shift + 8));
+    if (threadIdx.x < 64) {
+        uint32_t count;
+        const uint32_t incl = slice_piece_scan(sl, (int) threadIdx.x, count);
+        if ((int) threadIdx.x == s) s_first = incl - count;
+    }
+    __syncthreads();
+    const size_t k0 = kb + (size_t) threadIdx.x * kFoldPerLane;
+    if (k0 >= sl.table_size) return;
+    const uint32_t b = (uint32_t) (k0 >> sl.shift) & (kMaxBuckets - 1), local = (uint32_t) (k0 & (((size_t) 1 << sl.shift) - 1));
+    const uint32_t *piece_prefix = sl.meta + (size_t) s * sl.meta_stride + kSlicePiecePrefix;
+    const uint32_t p0 = s_first + piece_prefix[b], p1 = s_first + piece_prefix[b + 1];
+    fold_pieces_at<float, 8>(target, partials, p0, p1, k0, local, sl.table_size, sl.shift, false, 1.f);
+}
+
+static bool scatter_paged_enabled() {
+    static const bool paged = [] { const char *e = getenv("ENOKI_HIP_SCATTER_PAGED"); return !e || atoi(e) != 0; }();
+    return paged;
+}
+
+bool scatter_add_sliced_applicable(size_t table_size, size_t n) {
+    constexpr size_t span = (size_t) kMaxBuckets * bins_of<float>;
+    return scatter_paged_enabled() && ctx().tuning.bucket_ordered && !ctx().tuning.deterministic && n >= ((size_t) 1 << 18) &&
+           n < ((size_t) 1 << 30) && table_size > span && table_size <= (size_t) kMaxSlices * span;
+}
+
+int scatter_add_sliced(float *base, size_t table_size, const float *value, const uint32_t *index, const Arg<uint8_t> &mask, size_t n) {
+    RoctxRange range("enoki-hip: scatter_add (slices, paged)");
+    Context &c = ctx();
+    constexpr int Shift = bin_shift_of<float>;
+    constexpr size_t Bins = bins_of<float>, span = (size_t) kMaxBuckets * Bins;
+    const int S = (int) ((table_size + span - 1) / span);
+    if (S < 2 || S > kMaxSlices) return fail(EK_ERR_UNSUPPORTED, "scatter_add_sliced(): %zu bins", table_size);
+    // the piece budget: what one unsliced call takes (one piece per CU) per slice up to FOUR slices -- never fewer pieces than the
+    // host-sized path gave a table of up to 16 Mi bins -- and no more beyond; dealt to the slices by population on the device (every
+    // populated bucket has a piece of its own on top).  With ONE call's budget over all slices a zipf-distributed index array, whose
+    // hot bin holds a quarter of the pairs, left that bin to 64 pieces: accumulate 2.17 ms against 1.78 ms (64 Mi adds, K = 16 Mi).
+    const uint32_t budget = (uint32_t) bucket_target_pieces(n, kMaxBuckets) * (uint32_t) std::min(S, 4);
+    const size_t total_buckets = (table_size + Bins - 1) / Bins, max_pieces = (size_t) budget + (size_t) S + total_buckets;
+    CoarseSplit cs;
+    if (int rc = coarse_split<Shift + 8>(cs, value, index, mask, n, S, budget)) return rc;
+    // every slice with the geometry of a full one (256 buckets: 32-element pages) and the whole input as its bound
+    const PagedPlan plan = paged_plan(n, kMaxBuckets, c.num_cu);
+    if (plan.page_shift != 5 || plan.W > 1024) return fail(EK_ERR_UNSUPPORTED, "scatter_add_sliced(): %u workgroups", plan.W);
+    const size_t pool_pages = paged_slice_pool_pages(cs.elements, S, plan.W, plan.page_shift);
+    const uint32_t meta_stride = (kSlicePiecePrefix + kMaxBuckets + 1 + 3u) & ~3u, part_stride = plan.W * (uint32_t) kMaxBuckets + 1u;
+    Bucketed pool;                              // owns the page pool, the full-page list, all slices' glist_part and counter blocks
+    pool.type = EK_F32; pool.index_type = EK_U32; pool.op = EK_FMADD;
+    pool.n = n; pool.table_size = table_size;
+    pool.positions = pool_pages << plan.page_shift;
+    if (int rc = ek_hip_malloc(pool.positions * sizeof(uint16_t), &pool.pair_idx)) return rc;
+    if (int rc = ek_hip_malloc(pool.positions * sizeof(float), &pool.x_b)) return rc;
+    if (int rc = ek_hip_malloc((pool_pages + (size_t) S * part_stride) * sizeof(uint32_t), &pool.page_lists)) return rc;
+    if (int rc = ek_hip_malloc((size_t) S * meta_stride * sizeof(uint32_t), &pool.meta)) return rc;
+    Scratch work, partials;
+    if (int rc = work.alloc((2 * pool_pages + 3 * (size_t) plan.W * kMaxBuckets) * sizeof(uint32_t))) return rc;
+    if (int rc = partials.alloc(max_pieces * Bins * sizeof(float))) return rc;
+    uint32_t *glist_full = (uint32_t *) pool.page_lists, *glist_part = glist_full + pool_pages;
+    EK_HIP_CHECK(hipMemsetAsync(pool.meta, 0, (size_t) S * meta_stride * sizeof(uint32_t), c.stream));
+    note_launch("bucket_meta_clear", (size_t) S * meta_stride, (size_t) S * meta_stride * sizeof(uint32_t));
+    const Arg<uint8_t> all{ nullptr, 1, 0u };
+    for (int s = 0; s < S; ++s) {
+        Bucketed sub;
+        sub.type = EK_F32; sub.index_type = EK_U32; sub.op = EK_FMADD;
+        sub.n = n;                              // (the bound: the slice's own size is range[2 s + 1], on the device)
+        sub.table_size = std::min(span, table_size - (size_t) s * span);
+        sub.win_lo = 0;
+        sub.win_span = (uint32_t) sub.table_size;
+        PagedSlice ps{ cs.range + 2 * s, (uint32_t) s * paged_slice_gap(plan.W, plan.page_shift), &plan, &pool, glist_full,
+                       (uint32_t *) work.ptr, pool_pages };
+        ps.meta = (uint32_t *) pool.meta + (size_t) s * meta_stride;
+        ps.glist_part = glist_part + (size_t) s * part_stride;
+        ps.piece_share = cs.share + s;
+        if (int rc = bucketed_create_paged<uint32_t>(&sub, (const float *) cs.x, (const uint32_t *) cs.idx, all, Shift, &ps)) return rc;
+    }
+    const SliceLists sl{ (const uint32_t *) pool.meta, glist_full, glist_part, meta_stride, part_stride, table_size, S, Shift };
+    constexpr int VV = 2;                       // as bucketed_accumulate<float, 1>
+    const size_t lds = Bins * sizeof(float);
+    if (int rc = allow_big_lds(k_bucket_accumulate_slices<VV>, lds)) return rc;
+    hipLaunchKernelGGL((k_bucket_accumulate_slices<VV>), dim3((unsigned) max_pieces), dim3(kBucketThreads), lds, c.stream,
+                       (float *) partials.ptr, (const uint16_t *) pool.pair_idx, (const float *) pool.x_b, sl);
+    EK_LAUNCH_CHECK("bucket_accumulate", n, n * (sizeof(uint16_t) + sizeof(float)) + max_pieces * Bins * sizeof(float));
+    hipLaunchKernelGGL(k_bin_fold_slices, dim3(fold_grid(table_size)), dim3(256), 0, c.stream, base, (const float *) partials.ptr, sl);
+    EK_LAUNCH_CHECK("scatter_add_fold", table_size, max_pieces * Bins * sizeof(float) + 2 * table_size * sizeof(float));
+    return EK_OK;
+}
+
 // ---- partition of an index array alone (ek_hip_index_partition_*) ------------------------------------------------------
 struct IndexPartition {
     ek_hip_index_partition_info info{};
@@ -1198,7 +1393,6 @@ struct ek_hip_bucketed : ek::Bucketed {
     bool slices_split = false;       // the slices hold disjoint parts of the input (CoarseSplit) instead of filtered views of all of it
     ~ek_hip_bucketed() { for (ek_hip_bucketed *s : slices) delete s; }
 };
-constexpr int kMaxSlices = 64;
 struct SliceCounts { const uint32_t *active[kMaxSlices]; const uint32_t *flag; };
 
 template <typename T, int ROp>

@@ -645,19 +645,13 @@ template <typename T, int C> struct FoldTargets { T *table[C]; T scale[C]; };   
 constexpr int kFoldPerLane = 4;
 inline unsigned fold_grid(size_t table_size) { return (unsigned) ((table_size + 256 * kFoldPerLane - 1) / (256 * kFoldPerLane)); }
 
-template <typename T, int C>
-__global__ __launch_bounds__(256) void k_bin_fold_pieces(FoldTargets<T, C> targets, const T *__restrict__ partials,
-                                                         const uint32_t *__restrict__ piece_prefix, size_t table_size,
-                                                         size_t partial_stride, unsigned fresh = 0u,
-                                                         int shift = bin_shift_of<T>) {
-    const size_t k0 = ((size_t) blockIdx.x * 256 + threadIdx.x) * kFoldPerLane;
-    if (k0 >= table_size) return;
+/// entries [k0, k0 + kFoldPerLane) of one table: old (unless fresh) + scale * the sum over pieces [p0, p1) of their bucket's partial tables
+/// Ahead > 1 (tables whose hot bucket may have a thousand pieces): that many pieces' loads in flight per round of the loop
+template <typename T, int Ahead = 1>
+__device__ __forceinline__ void fold_pieces_at(T *__restrict__ target, const T *__restrict__ partials, const uint32_t p0, const uint32_t p1,
+                                               const size_t k0, const uint32_t local, const size_t table_size, const int shift,
+                                               const bool is_fresh, const T scale) {
     using U = wrap_t<T>;
-    T *__restrict__ target = targets.table[blockIdx.y];
-    partials += (size_t) blockIdx.y * partial_stride;
-    const uint32_t b = (uint32_t) (k0 >> shift), local = (uint32_t) (k0 & (((size_t) 1 << shift) - 1));
-    const bool is_fresh = (fresh >> blockIdx.y) & 1u;       // fresh: the table holds no data yet, its sums are written
-    const uint32_t p0 = piece_prefix[b], p1 = piece_prefix[b + 1];
     U sum[kFoldPerLane];
     T old[kFoldPerLane];
 #pragma unroll
@@ -670,7 +664,19 @@ __global__ __launch_bounds__(256) void k_bin_fold_pieces(FoldTargets<T, C> targe
 #pragma unroll
                 for (int j = 0; j < 4; ++j) old[j] = t.v[j];
             }
-            for (uint32_t p = p0; p < p1; ++p) {
+            uint32_t p = p0;
+            if constexpr (Ahead > 1) {
+                for (; p + Ahead <= p1; p += Ahead) {
+                    Pack<T, 4> v[Ahead];
+#pragma unroll
+                    for (int a = 0; a < Ahead; ++a) v[a] = pack_load<T, 4, true>(partials + ((size_t) (p + a) << shift) + local);
+#pragma unroll
+                    for (int a = 0; a < Ahead; ++a)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) sum[j] = (U) (sum[j] + (U) v[a].v[j]);
+                }
+            }
+            for (; p < p1; ++p) {
                 const Pack<T, 4> v = pack_load<T, 4, true>(partials + ((size_t) p << shift) + local);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) sum[j] = (U) (sum[j] + (U) v.v[j]);
@@ -689,8 +695,7 @@ __global__ __launch_bounds__(256) void k_bin_fold_pieces(FoldTargets<T, C> targe
     for (int j = 0; j < kFoldPerLane; ++j) {
         U v = sum[j];
         if constexpr (std::is_floating_point_v<T>) {
-            const T f = targets.scale[blockIdx.y];
-            if (f != T(1)) v = v * f;
+            if (scale != T(1)) v = v * scale;
         }
         out[j] = (T) ((U) old[j] + v);
     }
@@ -706,6 +711,21 @@ __global__ __launch_bounds__(256) void k_bin_fold_pieces(FoldTargets<T, C> targe
         for (int j = 0; j < kFoldPerLane; ++j)
             if (k0 + j < table_size) target[k0 + j] = out[j];
     }
+}
+
+template <typename T, int C>
+__global__ __launch_bounds__(256) void k_bin_fold_pieces(FoldTargets<T, C> targets, const T *__restrict__ partials,
+                                                         const uint32_t *__restrict__ piece_prefix, size_t table_size,
+                                                         size_t partial_stride, unsigned fresh = 0u,
+                                                         int shift = bin_shift_of<T>) {
+    const size_t k0 = ((size_t) blockIdx.x * 256 + threadIdx.x) * kFoldPerLane;
+    if (k0 >= table_size) return;
+    T *__restrict__ target = targets.table[blockIdx.y];
+    partials += (size_t) blockIdx.y * partial_stride;
+    const uint32_t b = (uint32_t) (k0 >> shift), local = (uint32_t) (k0 & (((size_t) 1 << shift) - 1));
+    const bool is_fresh = (fresh >> blockIdx.y) & 1u;       // fresh: the table holds no data yet, its sums are written
+    const uint32_t p0 = piece_prefix[b], p1 = piece_prefix[b + 1];
+    fold_pieces_at<T>(target, partials, p0, p1, k0, local, table_size, shift, is_fresh, targets.scale[blockIdx.y]);
 }
 
 struct Scratch {

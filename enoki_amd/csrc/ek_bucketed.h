@@ -127,9 +127,9 @@ struct PieceRange {
     uint32_t pieces;                 // of the bucket this piece belongs to
 };
 
-// piece `blockIdx.x` -> its bucket and its share of the bucket's elements (the same cut as k_bin_accumulate)
+// piece `piece` of the lists -> its bucket and its share of the bucket's elements (the same cut as k_bin_accumulate); workgroup-uniform
 template <int PS>
-__device__ __forceinline__ bool bucket_piece(const BucketLists &bl, int &bucket, PieceRange &r) {
+__device__ __forceinline__ bool bucket_piece_at(const BucketLists &bl, const uint32_t piece, int &bucket, PieceRange &r) {
     // ONE round trip to global memory: every thread asks for everything its candidate bucket would need (prefix, bases) at once and
     // the thread whose bucket holds this piece publishes it -- the search, then the prefix of the bucket found, then its bases were
     // four dependent round trips, ~2.4 us at the start of every workgroup (profiles/probe_early_phases_r06.txt: "which piece am I")
@@ -139,14 +139,14 @@ __device__ __forceinline__ bool bucket_piece(const BucketLists &bl, int &bucket,
     for (int b = threadIdx.x; b < n_buckets; b += blockDim.x) {
         const uint32_t pp0 = bl.piece_prefix[b], pp1 = bl.piece_prefix[b + 1], lo = bl.base[b], hi = bl.base[b + 1];
         const uint32_t plo = PS ? bl.base_part[b] : 0u, phi = PS ? bl.base_part[b + 1] : 0u;
-        if (pp0 <= blockIdx.x && blockIdx.x < pp1) {
+        if (pp0 <= piece && piece < pp1) {
             s_piece[0] = (uint32_t) b; s_piece[1] = pp0; s_piece[2] = pp1; s_piece[3] = lo; s_piece[4] = hi; s_piece[5] = plo; s_piece[6] = phi;
         }
     }
-    if (blockIdx.x >= total) return false;
+    if (piece >= total) return false;
     __syncthreads();
     bucket = (int) s_piece[0];
-    const size_t q = blockIdx.x - s_piece[1], pieces = s_piece[2] - s_piece[1];
+    const size_t q = piece - s_piece[1], pieces = s_piece[2] - s_piece[1];
     auto cut = [&](size_t lo, size_t hi, size_t &b0, size_t &b1) {
         const size_t per = (hi - lo + pieces - 1) / pieces;
         b0 = lo + q * per < hi ? lo + q * per : hi;
@@ -164,6 +164,12 @@ __device__ __forceinline__ bool bucket_piece(const BucketLists &bl, int &bucket,
         r.p0 = (uint32_t) a; r.p1 = (uint32_t) b;
     }
     return true;
+}
+
+// piece `blockIdx.x`: one launch per object
+template <int PS>
+__device__ __forceinline__ bool bucket_piece(const BucketLists &bl, int &bucket, PieceRange &r) {
+    return bucket_piece_at<PS>(bl, blockIdx.x, bucket, r);
 }
 
 // Walks a piece.  Body:
@@ -636,6 +642,7 @@ struct Bucketed {
     uint32_t win_lo = 0, win_span = 0;     // a slice of a large table: only indices in [win_lo, win_lo + win_span) (ek_hip_bucketed::slices)
     bool correct_masked = true;            // the final reduction adds the masked-out lanes' map_op(0) terms (slices: their owner does)
     Bucketed *owner = nullptr;             // a slice of a split table: pair_idx / x_b / u_b / m_b are the owner's page pool (not owned)
+    bool meta_borrowed = false;            // ... whose counter block and glist_part are parts of ONE allocation of the caller (PagedSlice::meta)
 
     bool has_mask = false;
     // (with or without a mask array: lanes whose index points outside the table are dropped by the partition too, and count like

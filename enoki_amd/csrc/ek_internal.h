@@ -183,6 +183,11 @@ constexpr inline bool unary_chainable(int op) {
 bool scatter_add_paged_applicable(size_t table_size, size_t n);
 int scatter_add_paged(float *base, size_t table_size, const float *value, const uint32_t *index, const Arg<uint8_t> &mask, size_t n);
 
+// ... and into a table beyond 256 buckets (up to 64 slices of 4 Mi bins): split by slice, one page pool, one accumulate and one fold
+// launch over all slices, sized on the device -- no read-back, capturable (bucketed.hip)
+bool scatter_add_sliced_applicable(size_t table_size, size_t n);
+int scatter_add_sliced(float *base, size_t table_size, const float *value, const uint32_t *index, const Arg<uint8_t> &mask, size_t n);
+
 bool scatter_add_binned_multi_applicable(size_t table_size, size_t n, bool index_is_array, size_t elem_size = 4);
 template <typename T, typename I, int C>
 int scatter_add_binned_multi(T *const *bases, size_t table_size, const Arg<T> *values, const Arg<T> *weights, unsigned weighted,

@@ -577,7 +577,9 @@ constexpr int kPgDirSlices = 4;
 // bases of both lists; pieces for the consumers (as k_bin_scan_buckets: a share of `target_pieces` in proportion to the
 // bucket's population, at least one when it is not empty).  Grid: (bucket, slice of the bucket's list).
 // DevRange: the directory of one slice of a split input (k_page_partition<..., DevRange>): the workgroups' page slots and the
-// slice's place in the pool's full-page lists follow from range[0 .. 1] as in the partition; bases are pool positions.
+// slice's place in the pool's full-page lists follow from range[0 .. 1] as in the partition; bases are pool positions.  Such a
+// launch has no class weights to feed back; its `class_stamp`, when not null, is ONE word instead: the pieces this slice may have
+// (its share of a budget over all slices, dealt on the device: scatter_add_sliced), in place of `target_pieces`.
 template <bool DevRange = false>
 static __global__ __launch_bounds__(256) void k_page_directory(uint32_t *__restrict__ glist_full, uint32_t *__restrict__ glist_part,
                                                                uint32_t *__restrict__ base_full, uint32_t *__restrict__ base_part,
@@ -599,6 +601,7 @@ static __global__ __launch_bounds__(256) void k_page_directory(uint32_t *__restr
         pool0 = (range[0] >> page_shift) + range_page0;
         range_tiles = ((size_t) range[1] + kPgTile - 1) / kPgTile;
         glist_full += pool0;
+        if (class_stamp) target_pieces = class_stamp[0];
     }
     // everything this workgroup reads from global memory, requested up front
     uint32_t f = 0, p = 0;

@@ -189,6 +189,10 @@ int scatter_add_binned_multi(T *const *bases, size_t table_size, const Arg<T> *v
 // slice is then an ordinary binned scatter_add on `base + slice * 4 Mi`.  The slice populations are read back once
 // (the only synchronisation).  Versus the global-atomic fallback this is ~5x faster on uniform indices and does not
 // collapse on skewed ones (same-address device atomics retire at 0.08 G/s).
+// float32 value arrays into up to 64 slices do not come here: scatter_add_sliced() (bucketed.hip) keeps the populations on the
+// device -- no read-back, one accumulate and one fold launch over all slices -- and can be part of a captured step graph.  What
+// remains on this host-sized path: 8-byte and integer element types, scalar operands, calls outside the paged path's tuning conditions,
+// tables beyond 64 slices.
 template <typename T> constexpr int super_shift_of = bin_shift_of<T> + 8;       // 2^22 (2^21 for 8-byte types) bins per super-bucket
 
 template <typename T, int N> __global__ __launch_bounds__(256) void k_scatter_add_pairs(T *__restrict__ base, const T *__restrict__ val,
@@ -204,6 +208,15 @@ template <typename T, int N> __global__ __launch_bounds__(256) void k_scatter_ad
 template <typename T, typename I>
 int scatter_add_binned_large(T *base, size_t table_size, const Arg<T> &value, const Arg<I> &index, const Arg<uint8_t> &mask,
                              size_t n) {
+    if constexpr (std::is_same_v<T, float>) {
+        // (valid int32 indices are non-negative: same bits as uint32)
+        if (value.vec && index.vec && scatter_add_sliced_applicable(table_size, n)) {
+            // (a shape the page pool's plan refuses, no memory for the pool: the host-sized path below handled every such call before)
+            const int rc = scatter_add_sliced(base, table_size, value.ptr, reinterpret_cast<const uint32_t *>(index.ptr), mask, n);
+            if (rc != EK_ERR_UNSUPPORTED && rc != EK_ERR_OOM) return rc;
+            (void) hipGetLastError();
+        }
+    }
     Context &c = ctx();
     constexpr int kSuperShift = super_shift_of<T>;
     constexpr size_t kSuperBins = (size_t) 1 << kSuperShift;
@@ -243,7 +256,13 @@ int scatter_add_binned_large(T *base, size_t table_size, const Arg<T> &value, co
                                                 n * (sizeof(uint32_t) + sizeof(T)));
 
     std::vector<uint32_t> offsets((size_t) n_super + 1);
-    if (int busy = refuse_while_capturing("scatter_add into a table of more than 4 Mi bins (slice populations are read back)")) return busy;
+    // (only the shapes that scatter_add_sliced() does not take arrive here)
+    constexpr const char *type_name = std::is_same_v<T, float> ? "float32" : std::is_same_v<T, double> ? "float64" :
+                                      std::is_same_v<T, uint32_t> ? "32-bit integer" : "64-bit integer";
+    char what[160];
+    snprintf(what, sizeof(what), "scatter_add of %s values into a table of more than %d Mi bins through the host-sized path (slice "
+             "populations are read back)", type_name, (int) (kSuperBins >> 20));
+    if (int busy = refuse_while_capturing(what)) return busy;
     EK_HIP_CHECK(hipMemcpyAsync(offsets.data(), bucket_base, offsets.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
     EK_HIP_CHECK(hipStreamSynchronize(c.stream));
 

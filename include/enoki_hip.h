@@ -149,7 +149,9 @@ EK_API void **ek_hip_binding_slot(void);
    allocates comes from a pool private to the graph and stays reserved until ek_hip_graph_destroy(): the arrays that
    are alive when the capture ends (results, gradients) keep their addresses, and every replay refreshes their contents.
    Not capturable (fail with EK_ERR_INVALID / EK_ERR_HIP): anything that reads back to the host -- ek_hip_memcpy_to_host,
-   ek_hip_mask_reduce (all / any / count), deterministic scatter_add, ek_hip_profile_*.
+   ek_hip_mask_reduce (all / any / count), deterministic scatter_add under a mask array, ek_hip_profile_*, and a mode-0
+   scatter_add into more than 4 Mi bins (2 Mi for 8-byte types) on its host-sized path: 8-byte and integer element types, a
+   scalar value or index operand, tables beyond 256 Mi bins (see ek_hip_scatter_add).
    The reference has no counterpart: its cuda_eval() re-assembles and re-launches PTX per evaluation (jit.cu:1385-1471). */
 typedef struct ek_hip_graph ek_hip_graph;
 EK_API int ek_hip_graph_begin(void);
@@ -382,6 +384,12 @@ EK_API int ek_hip_scatter(int type, int index_type, void *base, const ek_operand
            reference's element-order accumulation (dynamic.h:517-534).  Needs `base_size` and an
            index array; under a mask ARRAY it synchronizes once (the number of active pairs is read back), otherwise not
            at all.  Integer types are exact in either mode.
+   Tables beyond 4 Mi bins (2 Mi for 8-byte types), mode 0, 256 Ki+ elements: the pairs are split by slice of the table first.
+   float32 value ARRAYS through a 32-bit index array into up to 256 Mi bins keep the slice populations on the device (one
+   page pool for all slices, one accumulate and one fold launch over all of them): no synchronisation, and the call -- from
+   here, per stream from ek_hip_scatter_add_multi, from Tape::backward() as the adjoint of a gather -- can be part of a captured
+   step graph.  Every other such call (8-byte and integer types, scalar operands, "bucket_ordered" = 0) reads the slice
+   populations back: it synchronises once, and under a capture it fails with EK_ERR_INVALID and leaves the capture valid.
    64-bit index arrays of 256 Ki+ elements into a table of known size <= 2^32 are narrowed once (the reference's tape
    records gather offsets as Int64, autodiff.cpp:355-366) and then take the same paths as 32-bit ones. */
 EK_API int ek_hip_scatter_add(int type, int index_type, void *base, size_t base_size,
