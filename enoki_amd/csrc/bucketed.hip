@@ -617,16 +617,17 @@ struct PagedSlice {
 };
 
 /// The same object from the single-pass paged partition (ek_paged.h): 4-byte element types, n <= 2^30.  One streaming pass
-/// over (index, x) + the page directory: no count pass, no scans.
+/// over (index, x) + the page directory: no count pass, no scans.  pages32: above 128 buckets the caller wants 8-byte records and
+/// 32-element pages instead of two planes and 64-element pages (a slice's plan says so itself).
 template <typename I>
 static int bucketed_create_paged(Bucketed *b, const float *x, const I *index, const Arg<uint8_t> &mask, int shift,
-                                 const PagedSlice *slice = nullptr) {
+                                 const PagedSlice *slice = nullptr, bool pages32 = false) {
     RoctxRange range("enoki-hip: bucket partition (pages)");
     Context &c = ctx();
     b->shift = shift;
     const size_t n = b->n;             // (a slice: the bound, the whole input)
     const int n_buckets = b->n_buckets = (int) ((b->table_size + ((size_t) 1 << shift) - 1) >> shift);
-    const PagedPlan p = slice ? *slice->plan : paged_plan(n, n_buckets, c.num_cu, c.tuning.xcd_balance != 0);
+    const PagedPlan p = slice ? *slice->plan : paged_plan(n, n_buckets, c.num_cu, c.tuning.xcd_balance != 0, false, pages32);
     if (p.W > 1024) return fail(EK_ERR_UNSUPPORTED, "ek_hip_bucketed_pair_create(): %u workgroups", p.W);
     b->page_shift = p.page_shift;
     b->positions = slice ? slice->pool_pages << p.page_shift : p.page_slots << p.page_shift;
@@ -717,7 +718,8 @@ static int bucketed_create_paged(Bucketed *b, const float *x, const I *index, co
     const int vec_ok = aligned16(index) && aligned16(x) && arg_aligned(mask);
     auto launch = [&](auto kernel) -> int {
         // the workgroup's own page directory in the LDS behind the records when it fits next to them and the kernel's static
-        // arrays (160 KiB per workgroup on gfx950: inputs up to ~64 Mi elements); ENOKI_HIP_WDIR_LDS=0: through global memory
+        // arrays (160 KiB per workgroup on gfx950: up to 128 buckets inputs up to ~64 Mi elements; the two planes of more than 128
+        // buckets leave ~8 KiB at 256 buckets, inputs up to ~28 Mi elements); ENOKI_HIP_WDIR_LDS=0: through global memory
         static const bool want = [] { const char *e = getenv("ENOKI_HIP_WDIR_LDS"); return !e || atoi(e) != 0; }();
         size_t lds = p.lds;
         out.wdir_lds = 0;
@@ -742,6 +744,8 @@ static int bucketed_create_paged(Bucketed *b, const float *x, const I *index, co
         if (p.page_shift != 5 || mask.vec) return fail(EK_ERR_INVALID, "bucketed_create_paged(): slice of an unexpected shape");
         rc = launch(k_page_partition<float, I, 5, false, false, true>);
     }
+    // (more than 128 buckets: records in two planes, 64-element pages from rings of 96 -- ek_paged.h)
+    else if (p.planes) rc = mask.vec ? launch(k_page_partition<float, I, 6, true, false, false, true>) : launch(k_page_partition<float, I, 6, false, false, false, true>);
     else if (p.page_shift == 6) rc = mask.vec ? launch(k_page_partition<float, I, 6, true>) : launch(k_page_partition<float, I, 6, false>);
     else rc = mask.vec ? launch(k_page_partition<float, I, 5, true>) : launch(k_page_partition<float, I, 5, false>);
     if (rc) return rc;
@@ -1083,7 +1087,10 @@ int scatter_add_paged(float *base, size_t table_size, const float *value, const 
     ek::Bucketed obj;
     obj.type = EK_F32; obj.index_type = EK_U32; obj.op = EK_FMADD;
     obj.n = n; obj.table_size = table_size;
-    if (int rc = bucketed_create_paged<uint32_t>(&obj, value, index, mask, bin_shift_of<float>)) return rc;
+    // 32-element pages above 128 buckets (2 - 4 Mi bins), by choice: the accumulation under the exchange locks does not gain from
+    // 64-element pages what the partition does and loses on skewed indices (64 Mi adds into 4 Mi bins, same call: uniform 319 -> 302 us,
+    // zipf(1.3) 1.96 -> 2.37 ms with bucket_accumulate 1.50 -> 1.99 ms; profiles/probe_paged_planes_r07.txt)
+    if (int rc = bucketed_create_paged<uint32_t>(&obj, value, index, mask, bin_shift_of<float>, nullptr, /* pages32 */ true)) return rc;
     BucketStreams<float, 1> st{};
     st.map_op[0] = EK_COPY; st.imm[0] = 0.f; st.scale[0] = 1.f;
     st.from_u = 0u; st.weighted = 1u; st.plain_x = 1u;
@@ -1221,8 +1228,8 @@ int scatter_add_sliced(float *base, size_t table_size, const float *value, const
     const size_t total_buckets = (table_size + Bins - 1) / Bins, max_pieces = (size_t) budget + (size_t) S + total_buckets;
     CoarseSplit cs;
     if (int rc = coarse_split<Shift + 8>(cs, value, index, mask, n, S, budget)) return rc;
-    // every slice with the geometry of a full one (256 buckets: 32-element pages) and the whole input as its bound
-    const PagedPlan plan = paged_plan(n, kMaxBuckets, c.num_cu);
+    // every slice with the geometry of a full one (256 buckets; the pool is built on 32-element pages) and the whole input as its bound
+    const PagedPlan plan = paged_plan(n, kMaxBuckets, c.num_cu, false, false, /* pages32 */ true);
     if (plan.page_shift != 5 || plan.W > 1024) return fail(EK_ERR_UNSUPPORTED, "scatter_add_sliced(): %u workgroups", plan.W);
     const size_t pool_pages = paged_slice_pool_pages(cs.elements, S, plan.W, plan.page_shift);
     const uint32_t meta_stride = (kSlicePiecePrefix + kMaxBuckets + 1 + 3u) & ~3u, part_stride = plan.W * (uint32_t) kMaxBuckets + 1u;
@@ -1488,8 +1495,8 @@ int ek_hip_bucketed_pair_create_masked(int type, int index_type, int op, const v
             if (split) {
                 rc = want_half ? coarse_split<bin_shift_of<float> - 1 + 8>(cs, (const float *) x, (const uint32_t *) index, m, n, S)
                                : coarse_split<bin_shift_of<float> + 8>(cs, (const float *) x, (const uint32_t *) index, m, n, S);
-                // every slice with the geometry of a full one (256 buckets: 32-element pages) and the whole input as its bound
-                pool_plan = paged_plan(n, kMaxBuckets, ctx().num_cu);
+                // every slice with the geometry of a full one (256 buckets; the pool is built on 32-element pages) and the whole input as its bound
+                pool_plan = paged_plan(n, kMaxBuckets, ctx().num_cu, false, false, /* pages32 */ true);
                 pool_pages = paged_slice_pool_pages(cs.elements, S, pool_plan.W, pool_plan.page_shift);
                 b->positions = pool_pages << pool_plan.page_shift;
                 if (rc == EK_OK) rc = ek_hip_malloc(b->positions * sizeof(uint16_t), &b->pair_idx);

@@ -7,13 +7,14 @@
 // element is written: a count pass over the indices (4 B/elt) and two scans.  And a workgroup that writes its share of a
 // bucket's run appends ~64 elements per tile at an arbitrary alignment: partially written cache lines, 2-byte stores,
 // 1.19x write amplification (profiles/rocprof_pmc_r03.txt) -- the write-out was 56 % of the kernel.
-// Here the output of a bucket is a LIST OF PAGES instead: a page is 64 elements (32 when the table has more than 128
-// buckets) = one full 128-byte line of 16-bit bucket-local indices + two full lines of values, written exactly once by 16-byte
-// stores.  Every workgroup owns a contiguous range of page slots and hands them out itself, so no offset depends on another
-// workgroup: no count pass, no scan, no look-back, no global atomics in the loop.
+// Here the output of a bucket is a LIST OF PAGES instead: a page is 64 elements (32 where a caller asks for it above 128
+// buckets: the page pools of sliced tables, the element-order scatter_add) = one full 128-byte line of 16-bit bucket-local
+// indices + two full lines of values, written exactly once by 16-byte stores.  Every workgroup owns a contiguous range of page
+// slots and hands them out itself, so no offset depends on another workgroup: no count pass, no scan, no look-back, no global
+// atomics in the loop.
 //
 //   k_page_partition   one 1024-thread workgroup per CU walks its chunk of (index, x) in tiles of 4096 elements.  Per bucket the
-//                      LDS holds a circular buffer of `cap` elements (16 Ki elements over all buckets = 96 KiB); an element
+//                      LDS holds a circular buffer of `cap` elements (see kPgLdsElems for the record layouts); an element
 //                      takes its slot with ONE returning LDS atomic on a {origin, fill} word, complete pages leave as 16-byte
 //                      vectors.  A tile that brings a bucket more than its buffer holds (skewed indices) takes further rounds
 //                      of the same three phases.  What is left at the end of the chunk leaves as one partially filled page per
@@ -32,8 +33,18 @@ namespace ek {
 
 constexpr int kPgThreads = 1024;
 constexpr int kPgTile = 4 * kPgThreads;
-constexpr int kPgLdsElems = 16384;             // elements staged per workgroup, all buckets together (128 KiB of 8-byte records)
+// Elements staged per workgroup, all buckets together, as 8-byte {value bits, local index} records: 128 KiB, a ring of
+// 16384 / n_buckets records per bucket (IndexOnly: 4-byte records, twice as many).  A ring has to hold a page and what one tile
+// brings on top, so above 128 buckets 8-byte records feed 32-element pages only.  Value partitions of more than 128 buckets
+// therefore stage TWO PLANES instead (round 7): xs[n_buckets][96] of value bits (4 B) and ls[n_buckets][96] of 16-bit local indices
+// -- 6 bytes per element, 144 KiB at 256 buckets next to 8 KiB of static arrays in the 160 KiB of a CU -- whose ring of 96 = 1.5
+// pages carries 64-element pages (kPgPlaneCap; the sliced-table pools and the element-order scatter_add stay on 8-byte records
+// and 32-element pages by choice of their callers: paged_plan(.., pages32 = true)).
+constexpr int kPgLdsElems = 16384;
+constexpr uint32_t kPgPlaneCap = 96;           // records per bucket of a two-plane ring: NOT a power of two, a multiple of 32
+constexpr uint32_t kPgPlaneSpare = 8;          // records behind each plane (the spare record; keeps what follows 16-byte aligned)
 constexpr uint32_t kNoPage = 0xFFFFFFFFu;
+constexpr int kPgJobCountShift = 16;           // jobs[] of a two-plane ring, bits 16 .. 22: how many records of the page leave the ring (0: all)
 // The counter block of a partition: kPgReplicas copies of the per-bucket page totals ([replica][full | partially filled][bucket]; a
 // workgroup adds to copy w % kPgReplicas, the directory launch adds the copies up), then the meta row.  ONE copy meant 256 workgroups
 // queueing on every word: device-scope atomics on one address are served one after the other (~40 ns each), and the workgroups wait
@@ -101,15 +112,31 @@ using PgV2 = __attribute__((ext_vector_type(2))) uint32_t;
 // the device on entry, workgroup w takes tiles [tiles w / W, tiles (w + 1) / W) of it, and its page slots start at a pool page that
 // follows from the same two numbers (paged_slice_pool), so that no host ever needs the slice's population.  `n`, `chunk` and
 // `slots` are the host's upper bounds (the LDS is sized by them).
-template <typename T, typename I, int PS, bool HasMask, bool IndexOnly = false, bool DevRange = false>
+//
+// Planes (round 7): the records are staged as two planes, xs[n_buckets][96] of value bits and ls[n_buckets][96] of 16-bit local
+// indices, in a ring of kPgPlaneCap = 96 records = 1.5 pages of 64 (`cap` is ignored).  What changes against a power-of-two ring
+// that holds whole pages:
+//   * a position is (origin + fill) mod 96 by compare and subtract; origins are 0, 32 or 64, so four consecutive records of a page
+//     (16 bytes of values, 8 bytes of indices in write_out) never straddle the wrap;
+//   * the origin half of the {origin, fill} word is kept below 96: the lane that announces a page knows the origin from its own
+//     old[k] and moves the word on by (next origin - origin) << 16 | -Page in ONE non-returning add (0 -> 64 -> 32 -> 0);
+//   * jobs[] carries the page's first record (a multiple of 32) instead of its page number within the ring;
+//   * a tile fills at most ONE page per bucket from the ring; in an overflow round the second page is half in the ring (fills
+//     64 .. 95: a job of 32 records) and half in the registers of the pending lanes (fills 96 .. 127: written directly).
+template <typename T, typename I, int PS, bool HasMask, bool IndexOnly = false, bool DevRange = false, bool Planes = false>
 __global__ __launch_bounds__(kPgThreads) void k_page_partition(PagedOut<T> out, const I *__restrict__ index, Arg<uint8_t> mask,
                                                                const T *__restrict__ x, size_t n, size_t chunk, int n_buckets,
                                                                int shift, uint32_t cap, uint32_t slots, int vec_ok) {
     static_assert(sizeof(T) == 4, "pages carry 4-byte values");
+    static_assert(!Planes || (!IndexOnly && PS == 6), "two planes: value partitions with 64-element pages");
     constexpr uint32_t Page = 1u << PS;
+    if constexpr (Planes) cap = kPgPlaneCap;
     extern __shared__ __align__(16) unsigned char lds_raw[];
     using Rec = std::conditional_t<IndexOnly, uint32_t, unsigned long long>;
     Rec *rec = reinterpret_cast<Rec *>(lds_raw);                                // [n_buckets][cap] of {value bits, local index} (IndexOnly: the local index alone)
+    // (Planes: [n_buckets][96] + spare of value bits, then the same of 16-bit local indices)
+    uint32_t *xs = reinterpret_cast<uint32_t *>(lds_raw);
+    uint16_t *ls = reinterpret_cast<uint16_t *>(xs + ((uint32_t) n_buckets * kPgPlaneCap + kPgPlaneSpare));
     __shared__ uint32_t cnt[kMaxBuckets];      // origin << 16 | fill of the bucket's circular buffer
     __shared__ uint32_t npg[kMaxBuckets];      // full pages written so far per bucket
     __shared__ uint32_t dbase[kMaxBuckets];    // overflowing bucket: first of its directly written pages (slot within the round)
@@ -158,19 +185,33 @@ __global__ __launch_bounds__(kPgThreads) void k_page_partition(PagedOut<T> out, 
         }
     }
     const size_t wbase = DevRange ? range_wbase : (size_t) w * slots;     // first page slot of this workgroup
+    // cap_pages: the WHOLE pages a ring holds (Planes: one, with half a page on top)
     const uint32_t lowmask = (1u << shift) - 1u, cap_pages = cap >> PS, cap_shift = 31u - (uint32_t) __builtin_clz(cap);
-    const uint32_t spare = (uint32_t) n_buckets << cap_shift;         // one record behind the buffers
+    const uint32_t spare = Planes ? (uint32_t) n_buckets * kPgPlaneCap : (uint32_t) n_buckets << cap_shift;   // one record behind the buffers
+    // record `at` = origin + fill of bucket b's ring (Planes: origin < cap and fill < cap, one subtraction wraps)
+    auto slot_of = [&](uint32_t b, uint32_t at) -> uint32_t {
+        if constexpr (Planes) return b * kPgPlaneCap + (at >= kPgPlaneCap ? at - kPgPlaneCap : at);
+        else return (b << cap_shift) | (at & (cap - 1u));
+    };
+    // the origin a ring has after `pages` pages have left it (Planes: 0 -> 64 -> 32 -> 0; else mod 2^16, a multiple of cap)
+    auto origin_after = [&](uint32_t org, uint32_t pages) -> uint32_t {
+        if constexpr (Planes) { const uint32_t o = org + (pages << PS); return o >= kPgPlaneCap ? o - kPgPlaneCap : o; }   // (pages <= 1)
+        else return (org + (pages << PS)) & 0xFFFFu;
+    };
     // The workgroup's own page directory (slot -> sequence number << 8 | bucket) is written while pages are announced and read
     // once, by the lists phase at the end.  Through global memory that read has to wait for ALL of the workgroup's stores (the
     // counter that orders them is in-order: 8-12 us at the end of every workgroup, profiles/probe_paged_phases_r05.txt); when
-    // the entries fit the LDS behind the records (inputs up to ~64 Mi elements) they stay there and nobody waits.
-    uint32_t *wd = reinterpret_cast<uint32_t *>(rec + spare + 2);
+    // the entries fit the LDS behind the records (inputs up to ~64 Mi elements; ~28 Mi next to the planes of 256 buckets) they
+    // stay there and nobody waits.
+    uint32_t *wd = Planes ? reinterpret_cast<uint32_t *>(ls + (spare + kPgPlaneSpare)) : reinterpret_cast<uint32_t *>(rec + spare + 2);
     for (int b = threadIdx.x; b < kMaxBuckets; b += kPgThreads) { cnt[b] = 0; npg[b] = 0; }
     if (threadIdx.x == 0) { s_pages = 0; s_jobs = 0; s_over = 0; }
     __syncthreads();
 
-    auto make_rec = [&](uint32_t xv, uint32_t local) -> Rec {
-        if constexpr (IndexOnly) return local; else return (unsigned long long) xv | ((unsigned long long) local << 32);
+    auto stage = [&](uint32_t slot, uint32_t xv, uint32_t local) {
+        if constexpr (Planes) { xs[slot] = xv; ls[slot] = (uint16_t) local; }
+        else if constexpr (IndexOnly) rec[slot] = local;
+        else rec[slot] = (unsigned long long) xv | ((unsigned long long) local << 32);
     };
     const uint8_t sm = mask.vec ? uint8_t(0) : arg_scalar(mask);
     // a tile as it arrives: nothing is decoded before the tile is placed, so that two tiles of loads stay in flight
@@ -248,16 +289,26 @@ __global__ __launch_bounds__(kPgThreads) void k_page_partition(PagedOut<T> out, 
         for (uint32_t j = g; j < njobs; j += kPgThreads / LX) {
             const uint32_t jb = jobs[j];
             if (jb == kNoPage) continue;
-            const uint32_t src = ((jb & 0xFFu) << cap_shift) + ((jb >> 8) << PS) + 4 * i;
             const size_t at = ((wbase + ps0 + j) << PS) + 4 * i;
-            if constexpr (IndexOnly) {
-                *reinterpret_cast<PgV4 *>(out.xp + at) = *reinterpret_cast<const PgV4 *>(rec + src);
+            if constexpr (Planes) {
+                // the planes are read as they are written out: 16 bytes of values, 8 bytes of indices per lane
+                // (a counted job: the half page of an overflow round -- the other half comes from the pending lanes' registers)
+                const uint32_t count = (jb >> kPgJobCountShift) & 0x7Fu;
+                if (count && 4 * i >= count) continue;
+                const uint32_t src = slot_of(jb & 0xFFu, ((jb >> 8) & 0x7Fu) + 4 * i);
+                *reinterpret_cast<PgV4 *>(out.xp + at) = *reinterpret_cast<const PgV4 *>(xs + src);
+                *reinterpret_cast<PgV2 *>(out.lp + at) = *reinterpret_cast<const PgV2 *>(ls + src);
             } else {
-                const PgV4 r01 = *reinterpret_cast<const PgV4 *>(rec + src), r23 = *reinterpret_cast<const PgV4 *>(rec + src + 2);
-                const PgV4 vx = { r01[0], r01[2], r23[0], r23[2] };
-                const PgV2 vl = { r01[1] | (r01[3] << 16), r23[1] | (r23[3] << 16) };
-                *reinterpret_cast<PgV4 *>(out.xp + at) = vx;
-                *reinterpret_cast<PgV2 *>(out.lp + at) = vl;
+                const uint32_t src = ((jb & 0xFFu) << cap_shift) + ((jb >> 8) << PS) + 4 * i;
+                if constexpr (IndexOnly) {
+                    *reinterpret_cast<PgV4 *>(out.xp + at) = *reinterpret_cast<const PgV4 *>(rec + src);
+                } else {
+                    const PgV4 r01 = *reinterpret_cast<const PgV4 *>(rec + src), r23 = *reinterpret_cast<const PgV4 *>(rec + src + 2);
+                    const PgV4 vx = { r01[0], r01[2], r23[0], r23[2] };
+                    const PgV2 vl = { r01[1] | (r01[3] << 16), r23[1] | (r23[3] << 16) };
+                    *reinterpret_cast<PgV4 *>(out.xp + at) = vx;
+                    *reinterpret_cast<PgV2 *>(out.lp + at) = vl;
+                }
             }
         }
     };
@@ -274,6 +325,10 @@ __global__ __launch_bounds__(kPgThreads) void k_page_partition(PagedOut<T> out, 
     // the bucket's elements beyond the buffer are complete pages + a rest, the pages get slots like any other and their
     // elements go STRAIGHT to global memory (4- and 2-byte stores, as the contiguous-run partition writes all of its output),
     // the rest is staged once the buffer has been written out.
+    // (Planes: the ring holds ONE whole page and half of the next.  An overflowing bucket's first page leaves the ring like any
+    // other; of its second page, if the tile completes it, fills 64 .. 95 leave the ring as a half job and fills 96 .. 127 go
+    // straight from the pending lanes' registers; if it does not, those 32 records stay and the pending lanes are staged behind
+    // them once the first page has left.)
     auto process = [&](const Tile &t) {
         uint32_t old[NE], pending = 0, done = 0;
         EK_PG_T(0);                       // waiting for the tile's loads + decode
@@ -282,9 +337,9 @@ __global__ __launch_bounds__(kPgThreads) void k_page_partition(PagedOut<T> out, 
         // staged without a branch: an element that found its bucket's buffer full (or is masked out) writes to a spare record
 #pragma unroll
         for (int k = 0; k < NE; ++k) {
-            const uint32_t b = t.ix[k] >> shift, fill = old[k] & 0xFFFFu, pos = ((old[k] >> 16) + fill) & (cap - 1u);
+            const uint32_t b = t.ix[k] >> shift, fill = old[k] & 0xFFFFu;
             const bool on = (t.on >> k) & 1u, ok = on && fill < cap;
-            rec[ok ? ((b << cap_shift) | pos) : spare] = make_rec(t.xv[k], t.ix[k] & lowmask);
+            stage(ok ? slot_of(b, (old[k] >> 16) + fill) : spare, t.xv[k], t.ix[k] & lowmask);
             pending |= (on && !ok) ? 1u << k : 0u;
             done |= (ok && ((fill + 1u) & (Page - 1u)) == 0u) ? 1u << k : 0u;
         }
@@ -317,7 +372,8 @@ __global__ __launch_bounds__(kPgThreads) void k_page_partition(PagedOut<T> out, 
                     if ((done >> k) & 1u) {
                         const uint32_t ps = wave_first + before[k] + below(dm[k]);
                         const uint32_t b = t.ix[k] >> shift, fill = old[k] & 0xFFFFu, pos = ((old[k] >> 16) + fill) & (cap - 1u);
-                        jobs[ps - ps0] = b | ((pos >> PS) << 8);
+                        // (Planes: the page is fills 0 .. 63, its first record is the origin itself)
+                        jobs[ps - ps0] = b | ((Planes ? old[k] >> 16 : pos >> PS) << 8);
                         const uint32_t entry = ((seq[k] + (fill >> PS)) << 8) | b;
                         if (out.wdir_lds) wd[ps] = entry; else out.wdir[wbase + ps] = entry;
                     }
@@ -334,7 +390,8 @@ __global__ __launch_bounds__(kPgThreads) void k_page_partition(PagedOut<T> out, 
                 if (f > cap) {
                     const uint32_t nd = (f >> PS) - cap_pages, p = nd ? atomicAdd(&s_pages, nd) : ps0, seq0 = npg[b] + cap_pages;
                     for (uint32_t q = 0; q < nd; ++q) {
-                        jobs[p - ps0 + q] = kNoPage;
+                        // (Planes: the ring holds the first half of the first of these pages, fills 64 .. 95 at origin + 64)
+                        jobs[p - ps0 + q] = Planes && q == 0 ? ((Page / 2) << kPgJobCountShift) | b | (origin_after(c >> 16, 1u) << 8) : kNoPage;
                         if (out.wdir_lds) wd[p + q] = ((seq0 + q) << 8) | b; else out.wdir[wbase + p + q] = ((seq0 + q) << 8) | b;
                     }
                     dbase[b] = p - ps0;
@@ -351,7 +408,9 @@ __global__ __launch_bounds__(kPgThreads) void k_page_partition(PagedOut<T> out, 
             for (int k = 0; k < NE; ++k) {
                 if ((done >> k) & 1u) {
                     const uint32_t b = t.ix[k] >> shift;
-                    atomicAdd(&cnt[b], (Page << 16) - Page);          // origin + Page, fill - Page
+                    // origin + Page, fill - Page (Planes: the origin stays below 96 -- this lane knows it from its own old[k])
+                    if constexpr (Planes) atomicAdd(&cnt[b], ((origin_after(old[k] >> 16, 1u) - (old[k] >> 16)) << 16) - Page);
+                    else atomicAdd(&cnt[b], (Page << 16) - Page);
                     atomicAdd(&npg[b], 1u);
                 }
             }
@@ -361,7 +420,8 @@ __global__ __launch_bounds__(kPgThreads) void k_page_partition(PagedOut<T> out, 
                 if ((pending >> k) & 1u) {
                     const uint32_t b = t.ix[k] >> shift, fill = old[k] & 0xFFFFu;
                     if (fill < dtail[b]) {
-                        const size_t at = ((wbase + ps0 + dbase[b]) << PS) + (fill - cap);
+                        // (the directly written pages follow the ring's whole pages; Planes: from fill 96 on, the second half of the first)
+                        const size_t at = ((wbase + ps0 + dbase[b]) << PS) + (fill - (cap_pages << PS));
                         if constexpr (IndexOnly) {
                             reinterpret_cast<uint32_t *>(out.xp)[at] = t.ix[k] & lowmask;
                         } else {
@@ -376,8 +436,10 @@ __global__ __launch_bounds__(kPgThreads) void k_page_partition(PagedOut<T> out, 
             }
             if ((int) threadIdx.x < n_buckets) {
                 const uint32_t b = threadIdx.x, c = cnt[b], f = c & 0xFFFFu, org = c >> 16, np = f >> PS;
-                if (f > cap) cnt[b] = (org << 16) | (f & (Page - 1u));
-                else cnt[b] = (((org + (np << PS)) & 0xFFFFu) << 16) | (f & (Page - 1u));
+                // more pages than the ring holds whole: it has been emptied, the origin may stay; else its np pages have left it
+                // (Planes, 96 < f < 128: one page has left, fills 64 .. 95 stay where they are and the pending lanes follow them)
+                if (np > cap_pages || (!Planes && f > cap)) cnt[b] = (org << 16) | (f & (Page - 1u));
+                else cnt[b] = (origin_after(org, np) << 16) | (f - (np << PS));
                 npg[b] += np;
             }
             if (threadIdx.x == 0) s_over = 0u;
@@ -391,8 +453,10 @@ __global__ __launch_bounds__(kPgThreads) void k_page_partition(PagedOut<T> out, 
             for (int k = 0; k < NE; ++k) {
                 if ((pending >> k) & 1u) {
                     const uint32_t b = t.ix[k] >> shift;
-                    const uint32_t slot = (b << cap_shift) | (((old[k] >> 16) + (old[k] & 0xFFFFu)) & (cap - 1u));
-                    rec[slot] = make_rec(t.xv[k], t.ix[k] & lowmask);
+                    // (Planes: the origin may have moved on by a page -- the word's origin half is final since the barrier, the
+                    // next tile's arrivals touch its fill half only)
+                    const uint32_t org = Planes ? cnt[b] >> 16 : old[k] >> 16;
+                    stage(slot_of(b, org + (old[k] & 0xFFFFu)), t.xv[k], t.ix[k] & lowmask);
                 }
             }
         }
@@ -493,7 +557,9 @@ __global__ __launch_bounds__(kPgThreads) void k_page_partition(PagedOut<T> out, 
             if (b < n_buckets) {
                 uint32_t entry = kNoPage;
                 if (fl[j]) {
-                    jobs[p] = (uint32_t) b | (((org[j] >> PS) & (cap_pages - 1u)) << 8);
+                    // (the WHOLE page leaves, whatever lies behind its elements in the ring: a partially filled page written up to
+                    // its count alone left stale memory behind it, and the forward + adjoint kernel took 99 us instead of 87)
+                    jobs[p] = (uint32_t) b | ((Planes ? org[j] : (org[j] >> PS) & (cap_pages - 1u)) << 8);
                     entry = (uint32_t) ((wbase + ps0 + p) << 6) | (fl[j] - 1u);
                     ++p;
                     atomicAdd(&out.gtotal[(w % kPgReplicas) * 2u * kMaxBuckets + kMaxBuckets + b], 1u);
@@ -741,18 +807,23 @@ struct PagedPlan {
     int page_shift = 6;
     uint32_t cap = 0, W = 0, slots = 0;
     size_t chunk = 0, page_slots = 0;          // page_slots: W * slots (positions = page_slots << page_shift)
-    size_t lds = 0;
+    size_t lds = 0;                            // dynamic LDS of the records (the workgroup's page directory may follow, see wdir_lds)
+    bool planes = false;                       // records staged as two planes (k_page_partition<.., Planes>)
     bool balanced = false;                     // the launch may deal its tiles by class weights (slots are provisioned for it)
 };
 
-/// geometry of the paged partition of n elements into n_buckets buckets (4-byte values)
-static inline PagedPlan paged_plan(size_t n, int n_buckets, int num_cu, bool weighted = false, bool index_only = false) {
+/// Geometry of the paged partition of n elements into n_buckets buckets (4-byte values).  Up to 128 buckets: 8-byte records, rings
+/// of at least 128, 64-element pages.  Above: two planes, rings of 96, 64-element pages -- unless the caller asks for
+/// `pages32`: 8-byte records, rings of 64 and 32-element pages, the geometry the page pools of sliced tables are built on
+/// (paged_slice_gap, paged_slice_pool_pages).  index_only: 4-byte records, twice the ring, 64-element pages.
+static inline PagedPlan paged_plan(size_t n, int n_buckets, int num_cu, bool weighted = false, bool index_only = false,
+                                   bool pages32 = false) {
     PagedPlan p;
-    // (4-byte records: twice as many fit, 256 buckets keep two 64-element pages each)
-    p.page_shift = n_buckets > (index_only ? 256 : 128) ? 5 : 6;
+    p.planes = !index_only && !pages32 && n_buckets > 128;
+    p.page_shift = pages32 && !index_only && n_buckets > 128 ? 5 : 6;
     int nb2 = 2;
     while (nb2 < n_buckets) nb2 <<= 1;
-    p.cap = (uint32_t) ((index_only ? 2 * kPgLdsElems : kPgLdsElems) / nb2);
+    p.cap = p.planes ? kPgPlaneCap : (uint32_t) ((index_only ? 2 * kPgLdsElems : kPgLdsElems) / nb2);
     const size_t tiles = (n + kPgTile - 1) / kPgTile;
     p.W = (uint32_t) std::max<size_t>(1, std::min<size_t>((size_t) num_cu, tiles));
     p.chunk = ((tiles + p.W - 1) / p.W) * kPgTile;
@@ -767,7 +838,7 @@ static inline PagedPlan paged_plan(size_t n, int n_buckets, int num_cu, bool wei
         p.slots = (uint32_t) (((most * kPgTile) >> p.page_shift) + (size_t) n_buckets);
     }
     p.page_slots = (size_t) p.W * p.slots;
-    p.lds = ((size_t) n_buckets * p.cap + 2) * (index_only ? 4 : 8);
+    p.lds = p.planes ? ((size_t) n_buckets * kPgPlaneCap + kPgPlaneSpare) * 6 : ((size_t) n_buckets * p.cap + 2) * (index_only ? 4 : 8);
     return p;
 }
 

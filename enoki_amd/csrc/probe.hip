@@ -548,19 +548,21 @@ extern "C" EK_API int ek_hip_probe_page_partition(int nts, int index64, const vo
     EK_HIP_CHECK(hipMemsetAsync(meta, 0, kPgCounterWords * sizeof(uint32_t), c.stream));
     const Arg<uint8_t> m{ mask, 1, mask ? 1u : 0u };
     const int vec_ok = aligned16(index) && aligned16(x) && (!mask || aligned16(mask));
-#define EK_PP_LAUNCH(I, PS, HM)                                                                                                        \
+#define EK_PP_LAUNCH(I, PS, HM, ...)                                                                                                   \
     {                                                                                                                                  \
-        EK_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_page_partition<float, I, PS, HM>),                          \
+        EK_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_page_partition<float, I, PS, HM, ##__VA_ARGS__>),           \
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int) p.lds));                                   \
-        hipLaunchKernelGGL((k_page_partition<float, I, PS, HM>), dim3(p.W), dim3(kPgThreads), p.lds, c.stream, out, (const I *) index,  \
-                           m, x, n, p.chunk, n_buckets, shift, p.cap, p.slots, vec_ok);                                               \
+        hipLaunchKernelGGL((k_page_partition<float, I, PS, HM, ##__VA_ARGS__>), dim3(p.W), dim3(kPgThreads), p.lds, c.stream, out,     \
+                           (const I *) index, m, x, n, p.chunk, n_buckets, shift, p.cap, p.slots, vec_ok);                            \
     }
     (void) nts;
     if (index64) {
-        if (p.page_shift == 6) { if (mask) EK_PP_LAUNCH(uint64_t, 6, true) else EK_PP_LAUNCH(uint64_t, 6, false) }
+        if (p.planes) { if (mask) EK_PP_LAUNCH(uint64_t, 6, true, false, false, true) else EK_PP_LAUNCH(uint64_t, 6, false, false, false, true) }
+        else if (p.page_shift == 6) { if (mask) EK_PP_LAUNCH(uint64_t, 6, true) else EK_PP_LAUNCH(uint64_t, 6, false) }
         else { if (mask) EK_PP_LAUNCH(uint64_t, 5, true) else EK_PP_LAUNCH(uint64_t, 5, false) }
     } else {
-        if (p.page_shift == 6) { if (mask) EK_PP_LAUNCH(uint32_t, 6, true) else EK_PP_LAUNCH(uint32_t, 6, false) }
+        if (p.planes) { if (mask) EK_PP_LAUNCH(uint32_t, 6, true, false, false, true) else EK_PP_LAUNCH(uint32_t, 6, false, false, false, true) }
+        else if (p.page_shift == 6) { if (mask) EK_PP_LAUNCH(uint32_t, 6, true) else EK_PP_LAUNCH(uint32_t, 6, false) }
         else { if (mask) EK_PP_LAUNCH(uint32_t, 5, true) else EK_PP_LAUNCH(uint32_t, 5, false) }
     }
 #undef EK_PP_LAUNCH
