@@ -110,6 +110,10 @@ template <typename T, bool = std::is_floating_point_v<T>> struct wrap_type { usi
 template <typename T> struct wrap_type<T, false> { using type = std::make_unsigned_t<T>; };
 template <typename T> using wrap_t = typename wrap_type<T>::type;
 
+// identity of a sum: 0 for integers, -0.0 for floating point types (+0.0 is none: -0.0 + +0.0 = +0.0, so padding or
+// seeding a sum with it turns a run of negative zeros into +0.0)
+template <typename T> inline constexpr T sum_identity = std::is_floating_point_v<T> ? T(-0.0) : T(0);
+
 // Kernel-side view of an ek_operand
 template <typename T> struct Arg {
     const T *ptr;   // device pointer or nullptr

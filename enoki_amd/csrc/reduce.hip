@@ -556,11 +556,12 @@ template <typename T> uint64_t empty_identity_bits(int op) {
 // ---- inclusive prefix sum ------------------------------------------------------------------------
 // Three-phase scan: per-block sums -> scan of block sums (single block) -> per-block scan + offset.
 // Blocks own contiguous chunks so results are deterministic.  Only Tape::append_psum needs this
-// (autodiff.cpp:473-521); it is not on the timed path.
+// (autodiff.cpp:473-521); it is not on the timed path.  Sums start from, and idle lanes add, sum_identity<T> (-0.0 for
+// floating point types): a prefix of negative zeros sums to -0.0 like the reference's out[i] = out[i - 1] + a[i].
 template <typename T>
 __global__ __launch_bounds__(256) void k_scan_block_sums(T *__restrict__ sums, const T *__restrict__ in, size_t n, size_t chunk) {
     size_t begin = (size_t) blockIdx.x * chunk, end = begin + chunk < n ? begin + chunk : n;
-    T v = T(0);
+    T v = sum_identity<T>;
     for (size_t i = begin + threadIdx.x; i < end; i += 256) v += in[i];
     v = block_reduce<Reducer<EK_HSUM, T>>(v);
     if (threadIdx.x == 0) sums[blockIdx.x] = v;
@@ -569,7 +570,7 @@ __global__ __launch_bounds__(256) void k_scan_block_sums(T *__restrict__ sums, c
 template <typename T>
 __global__ void k_scan_sums_serial(T *__restrict__ sums, unsigned count) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
-        T run = T(0);
+        T run = sum_identity<T>;
         for (unsigned i = 0; i < count; ++i) { T s = sums[i]; sums[i] = run; run += s; }
     }
 }
@@ -582,12 +583,12 @@ __global__ __launch_bounds__(256) void k_scan_apply(T *__restrict__ out, const T
     T carry = sums[blockIdx.x];
     for (size_t base = begin; base < end; base += 256) {
         size_t i = base + threadIdx.x;
-        T v = i < end ? in[i] : T(0);
+        T v = i < end ? in[i] : sum_identity<T>;
         tile[threadIdx.x] = v;
         __syncthreads();
         // Hillis-Steele within the 256-tile
         for (int d = 1; d < 256; d <<= 1) {
-            T add = threadIdx.x >= (unsigned) d ? tile[threadIdx.x - d] : T(0);
+            T add = threadIdx.x >= (unsigned) d ? tile[threadIdx.x - d] : sum_identity<T>;
             __syncthreads();
             tile[threadIdx.x] += add;
             __syncthreads();

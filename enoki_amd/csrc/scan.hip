@@ -97,8 +97,9 @@ __global__ __launch_bounds__(256) void k_scan_lookback(T *__restrict__ out, cons
     __syncthreads();
     const size_t tile = s_tile, tile_base = tile * (size_t) kTileElems;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr T kZero = sum_identity<T>;                  // -0.0 for floating point: padding must not turn -0.0 into +0.0
 
-    // ---- load 4 rows (all in flight), scan each vector locally ----
+    // ---- load 16 rows (all in flight), scan each vector locally ----
     Pack<T, V> v[kScanRows];
 #pragma unroll
     for (int r = 0; r < kScanRows; ++r) {
@@ -107,7 +108,7 @@ __global__ __launch_bounds__(256) void k_scan_lookback(T *__restrict__ out, cons
             v[r] = pack_load<T, V, true>(in + e);
         } else {
 #pragma unroll
-            for (int j = 0; j < V; ++j) v[r].v[j] = e + j < n ? in[e + j] : T(0);
+            for (int j = 0; j < V; ++j) v[r].v[j] = e + j < n ? in[e + j] : kZero;
         }
     }
     T incl[kScanRows];             // (exclusive over the lanes: what is added to this lane's vector)
@@ -122,11 +123,11 @@ __global__ __launch_bounds__(256) void k_scan_lookback(T *__restrict__ out, cons
             if (lane >= d) s = (T) ((W) s + (W) up);
         }
         const T below = scan_shfl_up(s, 1);                     // exclusive prefix over the lanes of this wave
-        incl[r] = lane == 0 ? T(0) : below;
+        incl[r] = lane == 0 ? kZero : below;
         if (lane == 63) s_wave[r][wave] = s;
     }
     __syncthreads();
-    T aggregate = T(0);
+    T aggregate = kZero;
 #pragma unroll
     for (int r = 0; r < kScanRows; ++r)
 #pragma unroll
@@ -135,7 +136,7 @@ __global__ __launch_bounds__(256) void k_scan_lookback(T *__restrict__ out, cons
     // ---- publish, look back (all four waves: 256 predecessors per round trip), publish again ----
     __shared__ T s_part[4];
     __shared__ int s_found[4];
-    T exclusive = T(0);
+    T exclusive = kZero;
     if (tile == 0) {
         if (threadIdx.x == 0) scan_publish(desc, 0, kScanInclusive, aggregate);
     } else {
@@ -145,15 +146,15 @@ __global__ __launch_bounds__(256) void k_scan_lookback(T *__restrict__ out, cons
             // wave w inspects predecessors base - 64 w - lane; the nearest tile that already knows its inclusive prefix
             // ends the walk, everything nearer contributes its aggregate
             const long long t = base - (long long) threadIdx.x;
-            uint32_t st = kScanInclusive;                    // "tiles" before tile 0: inclusive prefix 0
-            T val = T(0);
+            uint32_t st = kScanInclusive;                    // "tiles" before tile 0: inclusive prefix 0 (the identity)
+            T val = kZero;
             do {
                 if (t >= 0) scan_poll(desc, (size_t) t, st, val);
                 if (__any(st == kScanInvalid)) __builtin_amdgcn_s_sleep(1);
             } while (__any(st == kScanInvalid));
             const unsigned long long have_prefix = __ballot(st == kScanInclusive);
             const int nearest = have_prefix ? __ffsll((long long) have_prefix) - 1 : 64;
-            T part = lane <= nearest ? val : T(0);
+            T part = lane <= nearest ? val : kZero;
 #pragma unroll
             for (int d = 32; d >= 1; d >>= 1) part = (T) ((W) part + (W) scan_shfl_xor(part, d));
             if (lane == 0) { s_part[wave] = part; s_found[wave] = have_prefix != 0; }

@@ -506,7 +506,10 @@ template <typename Value> auto Tape<Value>::append_psum(Index source) -> Index {
     if (source == 0) return 0;
     struct PrefixSum : Special {
         void forward(Detail *detail, Index target, const Edge &edge) const override {
-            Detail::accumulate(detail->node(target).grad, psum(detail->node(edge.source).grad));
+            Node &t = detail->node(target);
+            Value g = detail->node(edge.source).grad;
+            if (g.size() == 1 && t.size != 1) set_slices(g, t.size);      // a scalar seed (forward(x)) stands for t.size ones
+            Detail::accumulate(t.grad, psum(g));
         }
         void backward(Detail *detail, Index target, const Edge &edge) const override {
             Node &t = detail->node(target);
