@@ -46,7 +46,7 @@ EXPORTS = [
     "ek_hip_graph_launch_count", "ek_hip_graph_destroy", "ek_hip_sort_pairs", "ek_hip_reduce_map", "ek_hip_reduce_chain", "ek_hip_map_chain", "ek_hip_map_chain_product", "ek_hip_partition_class_state", "ek_hip_scatter_add_multi_map", "ek_hip_binding_slot",
     "ek_hip_dist_unique_id", "ek_hip_dist_init", "ek_hip_dist_world", "ek_hip_dist_shard_range", "ek_hip_dist_all_reduce",
     "ek_hip_dist_reduce_scatter", "ek_hip_dist_all_gather", "ek_hip_dist_finalize", "ek_hip_dist_rccl_path",
-    "ek_hip_bucketed_applicable", "ek_hip_bucketed_pair_create", "ek_hip_bucketed_pair_create_hinted", "ek_hip_bucketed_pair_create_masked", "ek_hip_bucketed_reduce", "ek_hip_bucketed_scatter_add", "ek_hip_bucketed_scatter_add_scaled", "ek_hip_bucketed_early_pair",
+    "ek_hip_bucketed_applicable", "ek_hip_bucketed_pair_create", "ek_hip_bucketed_pair_create_hinted", "ek_hip_bucketed_pair_create_masked", "ek_hip_bucketed_pair_create_scalar", "ek_hip_bucketed_reduce", "ek_hip_bucketed_scatter_add", "ek_hip_bucketed_scatter_add_scaled", "ek_hip_bucketed_early_pair",
     "ek_hip_bucketed_destroy", "ek_hip_index_partition_create", "ek_hip_index_partition_get", "ek_hip_index_partition_destroy", "ek_hip_gather_address",
 ]
 
@@ -498,7 +498,8 @@ def psum(a):
 
 class Bucketed:
     """u = op(A[index], x, C[index]) kept in bucket order (ek_hip_bucketed_*): reductions over map(u) and the adjoint
-    scatter_add of the two gathers without a lookup that leaves the CU.  Keeps A, C alive; x and index may be dropped."""
+    scatter_add of the two gathers without a lookup that leaves the CU.  Keeps A, C alive; x and index may be dropped.
+    C may be a python float: the host-scalar addend of `fmadd(gather(A, idx), x, c)`."""
 
     HINT_ADJOINT = 1
     HINT_BOUNDED = 2
@@ -506,6 +507,16 @@ class Bucketed:
     def __init__(self, op, A, x, C, index, hints=0, mask=None):
         self.A, self.C, self.dtype, self.K = A, C, A.dtype, A.n
         h = ctypes.c_void_p()
+        if not isinstance(C, Buf):
+            # a host scalar in place of the addend table (ek_hip_bucketed_pair_create_scalar); op may also be a raw op code
+            code = TERNARY[op] if isinstance(op, str) else int(op)
+            check(lib.ek_hip_bucketed_pair_create_scalar(A.ek, index.ek, code, ctypes.c_void_p(A.ptr),
+                                                         ctypes.c_uint64(_imm_bits(C, A.dtype)), ctypes.c_size_t(A.n),
+                                                         ctypes.c_void_p(x.ptr), ctypes.c_void_p(index.ptr),
+                                                         ctypes.c_void_p(mask.ptr if mask is not None else None),
+                                                         ctypes.c_size_t(index.n), ctypes.c_uint(hints), ctypes.byref(h)))
+            self.handle = h
+            return
         check(lib.ek_hip_bucketed_pair_create_masked(A.ek, index.ek, TERNARY[op], ctypes.c_void_p(A.ptr), ctypes.c_void_p(C.ptr),
                                                      ctypes.c_size_t(A.n), ctypes.c_void_p(x.ptr), ctypes.c_void_p(index.ptr),
                                                      ctypes.c_void_p(mask.ptr if mask is not None else None),

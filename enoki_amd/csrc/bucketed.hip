@@ -112,7 +112,7 @@ struct ForwardBody {
 template <typename T, int ROp, int V, int PS, bool FromKept = false>
 __global__ __launch_bounds__(kBucketThreads) void k_bucket_pair_forward(T *__restrict__ partials, T *__restrict__ u_out,
                                                                         const T *__restrict__ table_a, const T *__restrict__ table_c,
-                                                                        size_t table_size, int flip_a, int flip_c, int two,
+                                                                        T addend, size_t table_size, int flip_a, int flip_c, int two,
                                                                         const uint16_t *__restrict__ pair_idx,
                                                                         const T *__restrict__ x_b, const T *__restrict__ kept,
                                                                         BucketLists bl, int map_op, int keep_partner, int shift,
@@ -127,11 +127,11 @@ __global__ __launch_bounds__(kBucketThreads) void k_bucket_pair_forward(T *__res
     PieceRange range;
     const bool live = bucket_piece<PS>(bl, bucket, range);        // (workgroup-uniform; a launch has a few more workgroups than pieces)
     if (!live) {
-        if constexpr (ROp != EK_REDUCE_NONE) bucket_finish<T, ROp>(R::identity(), partials, fin.ticket, fin.out, fin.active, fin.n, fin.zero_op, wave_part, fin.counters);
+        if constexpr (ROp != EK_REDUCE_NONE) bucket_finish<T, ROp>(R::identity(), partials, fin.ticket, fin.out, fin.active, fin.n, fin.zero_op, wave_part, fin.counters, fin.zero_u);
         return;
     }
     if constexpr (!FromKept) {
-        stage_pair_slice<T, false>(rec, nullptr, table_a, table_c, (size_t) bucket * Bins, table_size, Bins, flip_a, flip_c);
+        stage_pair_slice<T, false>(rec, nullptr, table_a, table_c, addend, (size_t) bucket * Bins, table_size, Bins, flip_a, flip_c);
         __syncthreads();
     }
 
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(kBucketThreads) void k_bucket_pair_forward(T *__res
 #pragma unroll
             for (int d = 8; d >= 1; d >>= 1) v = R::combine(v, bucket_shfl_down(v, d));
         }
-        bucket_finish<T, ROp>(v, partials, fin.ticket, fin.out, fin.active, fin.n, fin.zero_op, wave_part, fin.counters);
+        bucket_finish<T, ROp>(v, partials, fin.ticket, fin.out, fin.active, fin.n, fin.zero_op, wave_part, fin.counters, fin.zero_u);
     }
 }
 
@@ -790,7 +790,7 @@ static int bucketed_forward_launch(Bucketed *b, void *out, int map_op, bool keep
         if (int rc = allow_big_lds(k_bucket_pair_forward<T, ROp, VV, PS>, lds)) return rc;
         hipLaunchKernelGGL((k_bucket_pair_forward<T, ROp, VV, PS>), dim3(b->max_pieces), dim3(kBucketThreads), lds, c.stream,
                            (T *) b->reduce_partials, keep ? (T *) *kept : (T *) nullptr, (const T *) b->table_a,
-                           (const T *) b->table_c, b->table_size, flip_a, flip_c, two, (const uint16_t *) b->pair_idx,
+                           (const T *) b->table_c, b->template addend<T>(), b->table_size, flip_a, flip_c, two, (const uint16_t *) b->pair_idx,
                            (const T *) b->x_b, (const T *) nullptr, b->lists(), map_op, partner ? 1 : 0, b->shift,
                            b->template finish<T>(out, map_op, ROp != EK_REDUCE_NONE));
     });
@@ -802,7 +802,7 @@ static int bucketed_forward_launch(Bucketed *b, void *out, int map_op, bool keep
     if constexpr (ROp != EK_REDUCE_NONE) {
         if (!b->ticket) {
             hipLaunchKernelGGL((k_bucket_reduce_final<T, ROp>), dim3(1), dim3(256), 0, c.stream, (T *) out,
-                               (const T *) b->reduce_partials, b->max_pieces, b->masked_ptr(), b->n, map_op);
+                               (const T *) b->reduce_partials, b->max_pieces, b->masked_ptr(), b->n, map_op, b->template dropped_u<T>());
             EK_LAUNCH_CHECK("reduce_stage2", (size_t) b->max_pieces, (size_t) b->max_pieces * sizeof(T) + sizeof(T));
         }
     }
@@ -816,7 +816,7 @@ static int bucketed_reduce_kept_launch(Bucketed *b, void *out, int map_op, const
     constexpr int VV = sizeof(T) == 8 ? 1 : 2;
     EK_BY_LAYOUT(b, {
         hipLaunchKernelGGL((k_bucket_pair_forward<T, ROp, VV, PS, true>), dim3(b->max_pieces), dim3(kBucketThreads), 0, c.stream,
-                           (T *) b->reduce_partials, (T *) nullptr, (const T *) nullptr, (const T *) nullptr, b->table_size, 0, 0, 0,
+                           (T *) b->reduce_partials, (T *) nullptr, (const T *) nullptr, (const T *) nullptr, T(0), b->table_size, 0, 0, 0,
                            (const uint16_t *) b->pair_idx, (const T *) b->x_b, (const T *) values, b->lists(), map_op, 0, b->shift,
                            b->template finish<T>(out, zero_op));
     });
@@ -824,7 +824,7 @@ static int bucketed_reduce_kept_launch(Bucketed *b, void *out, int map_op, const
     b->launched_reducing();
     if (!b->ticket) {
         hipLaunchKernelGGL((k_bucket_reduce_final<T, ROp>), dim3(1), dim3(256), 0, c.stream, (T *) out, (const T *) b->reduce_partials,
-                           b->max_pieces, b->masked_ptr(), b->n, zero_op);
+                           b->max_pieces, b->masked_ptr(), b->n, zero_op, b->template dropped_u<T>());
         EK_LAUNCH_CHECK("reduce_stage2", (size_t) b->max_pieces, (size_t) b->max_pieces * sizeof(T) + sizeof(T));
     }
     return EK_OK;
@@ -1404,14 +1404,14 @@ struct SliceCounts { const uint32_t *active[kMaxSlices]; const uint32_t *flag; }
 
 template <typename T, int ROp>
 __global__ __launch_bounds__(64) void k_slices_combine(T *__restrict__ out, const T *__restrict__ partial, int slices, SliceCounts counts,
-                                                       size_t n, int map_op) {
+                                                       size_t n, int map_op, T zero_u) {
     using R = ek::BucketReducer<ROp, T>;
     if (threadIdx.x != 0) return;
     T r = R::identity();
     size_t kept = 0;
     bool nonfinite = counts.flag && counts.flag[0];
     for (int s = 0; s < slices; ++s) { r = R::combine(r, partial[s]); kept += counts.active[s][0]; nonfinite = nonfinite || counts.active[s][1]; }
-    out[0] = ek::bucket_dropped_lanes<T, ROp>(r, n - kept, nonfinite, map_op);
+    out[0] = ek::bucket_dropped_lanes<T, ROp>(r, n - kept, nonfinite, map_op, zero_u);
 }
 
 // (tables of three or more slices under a mask: the split by slice drops the masked-out lanes before any page partition sees
@@ -1449,16 +1449,14 @@ int ek_hip_bucketed_pair_create_hinted(int type, int index_type, int op, const v
     return ek_hip_bucketed_pair_create_masked(type, index_type, op, table_a, table_c, table_size, x, index, nullptr, n, hints, out);
 }
 
-int ek_hip_bucketed_pair_create_masked(int type, int index_type, int op, const void *table_a, const void *table_c, size_t table_size,
-                                       const void *x, const void *index, const uint8_t *mask, size_t n, unsigned hints,
-                                       ek_hip_bucketed **out) {
-    if (int rc = ensure_init()) return rc;
-    if (!out || !table_a || !x || !index) return fail(EK_ERR_INVALID, "ek_hip_bucketed_pair_create(): null pointer");
-    if (!table_c && op != EK_MULADD)
-        return fail(EK_ERR_INVALID, "ek_hip_bucketed_pair_create(): a NULL addend table (the product gather(A, idx) * x alone) goes with EK_MULADD");
+/// the object of op(A[index], x, C[index]) (addend == nullptr), or of op(A[index], x, *addend) with a host scalar (table_c == nullptr)
+/// bad_op: what an op outside the seven returns (the table entry points have always said "unsupported", the scalar one says "invalid")
+static int bucketed_pair_create(int type, int index_type, int op, const void *table_a, const void *table_c, const uint64_t *addend,
+                                size_t table_size, const void *x, const void *index, const uint8_t *mask, size_t n, unsigned hints,
+                                ek_hip_bucketed **out, int bad_op) {
     *out = nullptr;
     if (op != EK_FMADD && op != EK_FMSUB && op != EK_FNMADD && op != EK_FNMSUB && op != EK_MULADD && op != EK_MULSUB && op != EK_NMULADD)
-        return fail(EK_ERR_UNSUPPORTED, "ek_hip_bucketed_pair_create(): op %d is neither of the fma family nor a product-then-sum", op);
+        return fail(bad_op, "ek_hip_bucketed_pair_create(): op %d is neither of the fma family nor a product-then-sum", op);
     if (!ek_hip_bucketed_applicable(type, index_type, table_size, n))
         return fail(EK_ERR_UNSUPPORTED, "ek_hip_bucketed_pair_create(): shape not covered (type %d, %zu lookups into %zu entries%s)",
                     type, n, table_size, ctx().tuning.deterministic ? ", deterministic mode" : "");
@@ -1466,6 +1464,7 @@ int ek_hip_bucketed_pair_create_masked(int type, int index_type, int op, const v
     b->type = type; b->index_type = index_type; b->op = op;
     b->n = n; b->table_size = table_size;
     b->table_a = table_a; b->table_c = table_c;
+    if (addend) { b->scalar_addend = true; b->addend_bits = *addend; }
     int rc;
     // valid int32 indices are non-negative: same bits as uint32
     // EK_BUCKETED_HINT_ADJOINT: buckets of half the size, so that a bucket's table slice AND its two gradient tables fit the LDS
@@ -1522,6 +1521,7 @@ int ek_hip_bucketed_pair_create_masked(int type, int index_type, int op, const v
                 sub->table_size = std::min(span, table_size - (size_t) sl * span);
                 sub->table_a = (const float *) table_a + (size_t) sl * span;
                 sub->table_c = table_c ? (const float *) table_c + (size_t) sl * span : nullptr;
+                sub->scalar_addend = b->scalar_addend; sub->addend_bits = b->addend_bits;      // (every slice stages the scalar)
                 sub->correct_masked = false;
                 if (split) {
                     // the slice's own elements (indices already local to the slice), as many as the device says -- n at most
@@ -1558,6 +1558,24 @@ int ek_hip_bucketed_pair_create_masked(int type, int index_type, int op, const v
     return EK_OK;
 }
 
+int ek_hip_bucketed_pair_create_masked(int type, int index_type, int op, const void *table_a, const void *table_c, size_t table_size,
+                                       const void *x, const void *index, const uint8_t *mask, size_t n, unsigned hints,
+                                       ek_hip_bucketed **out) {
+    if (int rc = ensure_init()) return rc;
+    if (!out || !table_a || !x || !index) return fail(EK_ERR_INVALID, "ek_hip_bucketed_pair_create(): null pointer");
+    if (!table_c && op != EK_MULADD)
+        return fail(EK_ERR_INVALID, "ek_hip_bucketed_pair_create(): a NULL addend table (the product gather(A, idx) * x alone) goes with EK_MULADD");
+    return bucketed_pair_create(type, index_type, op, table_a, table_c, nullptr, table_size, x, index, mask, n, hints, out, EK_ERR_UNSUPPORTED);
+}
+
+int ek_hip_bucketed_pair_create_scalar(int type, int index_type, int op, const void *table_a, uint64_t addend_bits, size_t table_size,
+                                       const void *x, const void *index, const uint8_t *mask, size_t n, unsigned hints,
+                                       ek_hip_bucketed **out) {
+    if (int rc = ensure_init()) return rc;
+    if (!out || !table_a || !x || !index) return fail(EK_ERR_INVALID, "ek_hip_bucketed_pair_create_scalar(): null pointer");
+    return bucketed_pair_create(type, index_type, op, table_a, nullptr, &addend_bits, table_size, x, index, mask, n, hints, out, EK_ERR_INVALID);
+}
+
 int ek_hip_bucketed_reduce(ek_hip_bucketed *b, int reduce_op, int map_op, void *out, int keep_values, int keep_op) {
     if (int rc = ensure_init()) return rc;
     if (!b || !out) return fail(EK_ERR_INVALID, "ek_hip_bucketed_reduce(): null pointer");
@@ -1574,7 +1592,7 @@ int ek_hip_bucketed_reduce(ek_hip_bucketed *b, int reduce_op, int map_op, void *
         }
         counts.flag = (const uint32_t *) b->meta;          // (tables of three or more slices under a mask; null otherwise)
         Context &c = ctx();
-#define EK_COMBINE(OP) hipLaunchKernelGGL((k_slices_combine<float, OP>), dim3(1), dim3(64), 0, c.stream, (float *) out, (const float *) partial.ptr, S, counts, b->n, map_op)
+#define EK_COMBINE(OP) hipLaunchKernelGGL((k_slices_combine<float, OP>), dim3(1), dim3(64), 0, c.stream, (float *) out, (const float *) partial.ptr, S, counts, b->n, map_op, b->dropped_u<float>())
         switch (reduce_op) {
             case EK_HSUM: EK_COMBINE(EK_HSUM); break;
             case EK_HPROD: EK_COMBINE(EK_HPROD); break;

@@ -367,7 +367,8 @@ __device__ __forceinline__ void bucket_finish_fixed_begin(long long iblock /* th
 }
 __device__ __forceinline__ void bucket_finish_fixed_end(const uint32_t *s_last_fixed /* shared */, float *__restrict__ partials,
                                                         uint32_t *__restrict__ ticket, float *__restrict__ out, const uint32_t *__restrict__ active,
-                                                        size_t n, int map_op, float *wave_part, long long *wave_ipart, uint32_t *__restrict__ counters) {
+                                                        size_t n, int map_op, float *wave_part, long long *wave_ipart, uint32_t *__restrict__ counters,
+                                                        float zero_u) {
     unsigned long long *ipartials = reinterpret_cast<unsigned long long *>(partials);
     uint32_t *fpartials = reinterpret_cast<uint32_t *>(ipartials + gridDim.x);
     __syncthreads();
@@ -394,22 +395,24 @@ __device__ __forceinline__ void bucket_finish_fixed_end(const uint32_t *s_last_f
         for (int d = 8; d >= 1; d >>= 1) { iv += bucket_shfl_down(iv, d); fv += bucket_shfl_down(fv, d); }
         if (threadIdx.x == 0) {
             const float r = (float) iv * 3.7252902984619140625e-9f /* 2^-28 */ + fv;
-            out[0] = bucket_dropped_lanes<float, EK_HSUM>(r, active ? n - (size_t) active[0] : 0, active && active[1], map_op);
+            out[0] = bucket_dropped_lanes<float, EK_HSUM>(r, active ? n - (size_t) active[0] : 0, active && active[1], map_op, zero_u);
             finish_ticket_reset(ticket);
         }
     }
 }
 
+// The body of the two kernels below.  addend / zero_op / zero_u: what is staged without an addend table, and what a dropped lane
+// contributes (map zero_op of zero_u) -- compile-time constants in k_bucket_pair_forward_adjoint (-0.0 and zero_op(0), folded), run-time
+// values in k_bucket_pair_forward_adjoint_scalar.
 template <typename T, int V, int PS, bool Fixed, bool Two>
-__global__ __launch_bounds__(kBucketThreads) void k_bucket_pair_forward_adjoint(T *__restrict__ partials, T *__restrict__ table_partials,
-                                                                                const T *__restrict__ table_a,
-                                                                                const T *__restrict__ table_c, size_t table_size,
-                                                                                int flip_a, int flip_c,
-                                                                                const uint16_t *__restrict__ pair_idx,
-                                                                                const T *__restrict__ x_b, BucketLists bl,
-                                                                                int map_op, int keep_op, int shift, BucketFinish<T> fin,
-                                                                                const uint32_t *__restrict__ xmax_bits, int S0,
-                                                                                uint32_t *__restrict__ piece_mode) {
+__device__ __forceinline__ void bucket_pair_forward_adjoint(T *__restrict__ partials, T *__restrict__ table_partials,
+                                                            const T *__restrict__ table_a, const T *__restrict__ table_c, const T addend,
+                                                            size_t table_size, int flip_a, int flip_c,
+                                                            const uint16_t *__restrict__ pair_idx, const T *__restrict__ x_b,
+                                                            const BucketLists &bl, int map_op, int keep_op, int shift,
+                                                            const BucketFinish<T> &fin, const int zero_op, const T zero_u,
+                                                            const uint32_t *__restrict__ xmax_bits, int S0,
+                                                            uint32_t *__restrict__ piece_mode) {
     extern __shared__ __align__(16) unsigned char lds_dynamic[];
     // Fixed: a STATIC block (records of 4 Ki entries + 4 Ki pairs of sums, whatever Bins is) -- its address is a constant of the
     // program, every LDS instruction of the walk carries it in its immediate offset
@@ -440,9 +443,9 @@ __global__ __launch_bounds__(kBucketThreads) void k_bucket_pair_forward_adjoint(
     if (!bucket_piece<PS>(bl, bucket, range)) {
         if constexpr (Fixed) {
             bucket_finish_fixed_begin(0ll, T(0), partials, fin.ticket, &s_last_fixed);
-            bucket_finish_fixed_end(&s_last_fixed, partials, fin.ticket, fin.out, fin.active, fin.n, fin.zero_op, wave_part, wave_ipart, fin.counters);
+            bucket_finish_fixed_end(&s_last_fixed, partials, fin.ticket, fin.out, fin.active, fin.n, zero_op, wave_part, wave_ipart, fin.counters, zero_u);
         }
-        else bucket_finish<T, EK_HSUM>(T(0), partials, fin.ticket, fin.out, fin.active, fin.n, fin.zero_op, wave_part, fin.counters);
+        else bucket_finish<T, EK_HSUM>(T(0), partials, fin.ticket, fin.out, fin.active, fin.n, zero_op, wave_part, fin.counters, zero_u);
         return;
     }
 #ifdef EK_EARLY_TIMING
@@ -453,7 +456,7 @@ __global__ __launch_bounds__(kBucketThreads) void k_bucket_pair_forward_adjoint(
     fx_t[0] = __builtin_readcyclecounter();           // piece known
 #endif
     [[maybe_unused]] uint32_t slice_max[2] = { 0u, 0u };
-    stage_pair_slice<T, true>(rec, tables, table_a, table_c, (size_t) bucket * Bins, table_size, Bins, flip_a, flip_c, Fixed ? slice_max : nullptr);
+    stage_pair_slice<T, true>(rec, tables, table_a, table_c, addend, (size_t) bucket * Bins, table_size, Bins, flip_a, flip_c, Fixed ? slice_max : nullptr);
     if constexpr (Fixed) {
         for (int j = threadIdx.x; j < 2 * 4096; j += kBucketThreads) reinterpret_cast<unsigned long long *>(tables)[j] = 0ull;     // both planes, whole areas
     }
@@ -509,6 +512,8 @@ __global__ __launch_bounds__(kBucketThreads) void k_bucket_pair_forward_adjoint(
         const uint32_t E = xm >> 23;
         locks = E >= 255u || (E < (uint32_t) S0 + 1u && xm != 0u);
         const uint32_t am = s_guard[0], cm = s_guard[1];         // (max |a|, max |c| over the slice as bits: behind the staging barrier)
+        // (a host-scalar addend is staged into every record like a table entry, so cm is |c| itself and the guard needs nothing of
+        //  its own for it: a NaN or infinite scalar sends every piece down the lock path, as a non-finite table entry would)
         const float ubound = __uint_as_float(am) * __uint_as_float(xm) + __uint_as_float(cm);
         const size_t piece_pages = (size_t) (range.f1 - range.f0) + (range.p1 - range.p0);
         if (am >= 0x7F800000u || cm >= 0x7F800000u || !(ubound < 1.0e18f) || (piece_pages << PS) >> (62 - S0)) locks = true;
@@ -610,8 +615,8 @@ __global__ __launch_bounds__(kBucketThreads) void k_bucket_pair_forward_adjoint(
         fx_t[4] = __builtin_readcyclecounter();           // tables written
     }
 #endif
-    if constexpr (Fixed) bucket_finish_fixed_end(&s_last_fixed, partials, fin.ticket, fin.out, fin.active, fin.n, fin.zero_op, wave_part, wave_ipart, fin.counters);
-    else bucket_finish<T, EK_HSUM>(v, partials, fin.ticket, fin.out, fin.active, fin.n, fin.zero_op, wave_part, fin.counters);
+    if constexpr (Fixed) bucket_finish_fixed_end(&s_last_fixed, partials, fin.ticket, fin.out, fin.active, fin.n, zero_op, wave_part, wave_ipart, fin.counters, zero_u);
+    else bucket_finish<T, EK_HSUM>(v, partials, fin.ticket, fin.out, fin.active, fin.n, zero_op, wave_part, fin.counters, zero_u);
 #ifdef EK_EARLY_TIMING
     if constexpr (Fixed) {
         if (threadIdx.x == 0 && fx_t[1]) {
@@ -627,6 +632,39 @@ __global__ __launch_bounds__(kBucketThreads) void k_bucket_pair_forward_adjoint(
         }
     }
 #endif
+}
+
+// Two tables, or the product alone: the arguments, the staged -0.0 and the dropped lanes' folded zero_op(0) of the kernel as it was
+// before a host scalar could be the addend -- the headline step runs THIS kernel (fin.zero_u is not looked at).
+template <typename T, int V, int PS, bool Fixed, bool Two>
+__global__ __launch_bounds__(kBucketThreads) void k_bucket_pair_forward_adjoint(T *__restrict__ partials, T *__restrict__ table_partials,
+                                                                                const T *__restrict__ table_a,
+                                                                                const T *__restrict__ table_c, size_t table_size,
+                                                                                int flip_a, int flip_c,
+                                                                                const uint16_t *__restrict__ pair_idx,
+                                                                                const T *__restrict__ x_b, BucketLists bl,
+                                                                                int map_op, int keep_op, int shift, BucketFinish<T> fin,
+                                                                                const uint32_t *__restrict__ xmax_bits, int S0,
+                                                                                uint32_t *__restrict__ piece_mode) {
+    bucket_pair_forward_adjoint<T, V, PS, Fixed, Two>(partials, table_partials, table_a, table_c, T(-0.0), table_size, flip_a, flip_c, pair_idx,
+                                                      x_b, bl, map_op, keep_op, shift, fin, fin.zero_op, T(0), xmax_bits, S0, piece_mode);
+}
+
+// A host-scalar addend (no addend table): the scalar and the dropped lanes' u are kernel arguments.  The fixed-point instantiations
+// sit AT the limit of scalar registers (106): the two sign flags travel as one argument (1: -a, 2: -c) and the dropped lanes'
+// function is map_op itself -- this kernel does not look at fin.zero_op, the launch below asserts that the two agree -- which pays
+// for the two new values (without: 103 VGPRs, two scalar registers spilled).
+template <typename T, int V, int PS, bool Fixed, bool Two>
+__global__ __launch_bounds__(kBucketThreads) void k_bucket_pair_forward_adjoint_scalar(T *__restrict__ partials, T *__restrict__ table_partials,
+                                                                                       const T *__restrict__ table_a, T addend,
+                                                                                       size_t table_size, int flips,
+                                                                                       const uint16_t *__restrict__ pair_idx,
+                                                                                       const T *__restrict__ x_b, BucketLists bl,
+                                                                                       int map_op, int keep_op, int shift, BucketFinish<T> fin,
+                                                                                       const uint32_t *__restrict__ xmax_bits, int S0,
+                                                                                       uint32_t *__restrict__ piece_mode) {
+    bucket_pair_forward_adjoint<T, V, PS, Fixed, Two>(partials, table_partials, table_a, nullptr, addend, table_size, flips & 1, flips & 2, pair_idx,
+                                                      x_b, bl, map_op, keep_op, shift, fin, map_op, fin.zero_u, xmax_bits, S0, piece_mode);
 }
 
 template <typename T>
@@ -649,24 +687,37 @@ int bucketed_forward_adjoint_launch(Bucketed *b, void *out, int map_op, int keep
     const size_t piece_bound = 2 * (b->n / std::max<size_t>(1, b->max_pieces - (size_t) b->n_buckets)) + 65536;
     const int S0 = std::min(fixed_shift_for(piece_bound), 48);
     uint32_t *modes = fixed ? reinterpret_cast<uint32_t *>(static_cast<char *>(b->early) + (size_t) 2 * b->max_pieces * Bins * slot) : nullptr;
-    auto go = [&](auto kernel) -> int {
-        if (int rc = allow_big_lds(kernel, lds)) return rc;
-        hipLaunchKernelGGL(kernel, dim3(b->max_pieces), dim3(kBucketThreads), lds, c.stream,
-                           (T *) b->reduce_partials, (T *) b->early, (const T *) b->table_a, (const T *) b->table_c, b->table_size,
-                           flip_a, flip_c, (const uint16_t *) b->pair_idx, (const T *) b->x_b, b->lists(), map_op, keep_op, b->shift,
-                           b->template finish<T>(out, map_op), fixed ? b->active + (kPgMetaResultXmax - kPgMetaResult) : nullptr, S0, modes);
+    const bool scalar = b->scalar_addend;
+    const uint32_t *xmax = fixed ? b->active + (kPgMetaResultXmax - kPgMetaResult) : nullptr;
+    auto go = [&](auto kernel, auto kernel_scalar) -> int {
+        if (int rc = scalar ? allow_big_lds(kernel_scalar, lds) : allow_big_lds(kernel, lds)) return rc;
+        const BucketFinish<T> fin = b->template finish<T>(out, map_op);
+        if (scalar) {
+            // (k_bucket_pair_forward_adjoint_scalar applies map_op to the dropped lanes' u without looking at fin.zero_op)
+            if (fin.zero_op != map_op || b->table_c) return fail(EK_ERR_INVALID, "bucketed_forward_adjoint_launch(): inconsistent scalar-addend object");
+            hipLaunchKernelGGL(kernel_scalar, dim3(b->max_pieces), dim3(kBucketThreads), lds, c.stream,
+                               (T *) b->reduce_partials, (T *) b->early, (const T *) b->table_a, b->template addend<T>(), b->table_size,
+                               flip_a | (flip_c << 1), (const uint16_t *) b->pair_idx, (const T *) b->x_b, b->lists(), map_op, keep_op, b->shift,
+                               fin, xmax, S0, modes);
+        } else {
+            hipLaunchKernelGGL(kernel, dim3(b->max_pieces), dim3(kBucketThreads), lds, c.stream,
+                               (T *) b->reduce_partials, (T *) b->early, (const T *) b->table_a, (const T *) b->table_c, b->table_size,
+                               flip_a, flip_c, (const uint16_t *) b->pair_idx, (const T *) b->x_b, b->lists(), map_op, keep_op, b->shift,
+                               fin, xmax, S0, modes);
+        }
         return EK_OK;
     };
+#define EK_PAIR(PSV, FIXED, TWO) go(k_bucket_pair_forward_adjoint<T, VV, PSV, FIXED, TWO>, k_bucket_pair_forward_adjoint_scalar<T, VV, PSV, FIXED, TWO>)
     int rc;
     if constexpr (sizeof(T) == 8) {
-        rc = two ? go(k_bucket_pair_forward_adjoint<T, VV, 0, false, true>) : go(k_bucket_pair_forward_adjoint<T, VV, 0, false, false>);
+        rc = two ? EK_PAIR(0, false, true) : EK_PAIR(0, false, false);
     } else {
         if (fixed) lds = 0;            // (the fixed-point kernels' LDS is static)
-#define EK_GO(PSV) (fixed ? (two ? go(k_bucket_pair_forward_adjoint<T, VV, PSV, true, true>) : go(k_bucket_pair_forward_adjoint<T, VV, PSV, true, false>)) \
-                          : (two ? go(k_bucket_pair_forward_adjoint<T, VV, PSV, false, true>) : go(k_bucket_pair_forward_adjoint<T, VV, PSV, false, false>)))
+#define EK_GO(PSV) (fixed ? (two ? EK_PAIR(PSV, true, true) : EK_PAIR(PSV, true, false)) : (two ? EK_PAIR(PSV, false, true) : EK_PAIR(PSV, false, false)))
         rc = b->page_shift == 6 ? EK_GO(6) : EK_GO(5);
 #undef EK_GO
     }
+#undef EK_PAIR
     if (rc) return rc;
     EK_LAUNCH_CHECK("bucket_pair_fma_reduce_adjoint", b->n,
                     b->n * (sizeof(uint16_t) + sizeof(T)) + (b->table_c ? 2 : 1) * b->table_size * sizeof(T) + (size_t) 2 * b->max_pieces * Bins * slot);
@@ -678,7 +729,7 @@ int bucketed_forward_adjoint_launch(Bucketed *b, void *out, int map_op, int keep
     b->early_op = keep_op;
     if (!b->ticket) {
         hipLaunchKernelGGL((k_bucket_reduce_final<T, EK_HSUM>), dim3(1), dim3(256), 0, c.stream, (T *) out, (const T *) b->reduce_partials,
-                           b->max_pieces, b->masked_ptr(), b->n, map_op);
+                           b->max_pieces, b->masked_ptr(), b->n, map_op, b->template dropped_u<T>());
         EK_LAUNCH_CHECK("reduce_stage2", (size_t) b->max_pieces, (size_t) b->max_pieces * sizeof(T) + sizeof(T));
     }
     return EK_OK;

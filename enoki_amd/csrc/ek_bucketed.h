@@ -19,10 +19,12 @@ template <typename T> struct alignas(2 * sizeof(T)) PairRec { T a, c; };
 // doubles), and -- ZeroTables -- the two gradient tables behind them cleared.  A thread requests all of its entries before it
 // uses the first: the loop used to wait for each pair of loads (Bins / 1024 = 8 or 16 dependent round trips per piece, 6-10 us
 // of every launch).  Entries beyond the table read its last entry and count as zero.
+/// addend: what every record's c is when there is no addend table (uniform over the launch) -- the host scalar of
+/// `fmadd(gather(A, idx), x, c)`, or -0.0 for the product alone.  With a table it is not looked at.
 /// max_bits (optional, [2]): max |a|, max |c| over this thread's share of the slice as bit patterns (a NaN or an infinity comes out on top)
 template <typename T, bool ZeroTables>
 __device__ __forceinline__ void stage_pair_slice(PairRec<T> *rec, T *tables, const T *__restrict__ table_a, const T *__restrict__ table_c,
-                                                 size_t first, size_t table_size, int Bins, int flip_a, int flip_c, uint32_t *max_bits = nullptr) {
+                                                 T addend, size_t first, size_t table_size, int Bins, int flip_a, int flip_c, uint32_t *max_bits = nullptr) {
     constexpr int U = 8;
     const size_t last = table_size - 1;
     for (int j0 = threadIdx.x; j0 < Bins; j0 += U * (int) blockDim.x) {
@@ -32,7 +34,7 @@ __device__ __forceinline__ void stage_pair_slice(PairRec<T> *rec, T *tables, con
             const size_t k = first + (size_t) (j0 + u * (int) blockDim.x);
             const size_t kc = k < last ? k : last;
             a[u] = table_a[kc];
-            c[u] = table_c ? table_c[kc] : T(-0.0);       // no addend table: u = a x + (-0) = a x, bit for bit (signed zeros included)
+            c[u] = table_c ? table_c[kc] : addend;        // no addend table: the scalar; -0.0 for the product alone, u = a x + (-0) = a x, bit for bit (signed zeros included)
             if (k > last) { a[u] = T(0); c[u] = T(0); }
         }
 #pragma unroll
@@ -77,8 +79,11 @@ template <typename T> struct BucketFinish {
     T *out;
     const uint32_t *active;
     size_t n;
-    int zero_op;             // what a dropped lane (u = 0) contributes, as a function of 0
+    int zero_op;             // what a dropped lane contributes, as a function of its u ...  (k_bucket_pair_forward_adjoint_scalar
+                             // takes its own map_op instead: the same value, checked at its launch)
     uint32_t *counters = nullptr;   // the object's block of partition counters (gtotal): cleared by the last workgroup for the block's next user
+    T zero_u = T(0);         // ... which is fma(0, x, c): 0 with an addend TABLE (its gather is masked out too) and for the product alone,
+                             // the signed host scalar when that is the addend (Bucketed::dropped_u)
 };
 
 template <typename T> __device__ __forceinline__ T bucket_shfl_down(T v, int delta) {
@@ -262,13 +267,14 @@ __device__ __forceinline__ void walk_piece(const BucketLists &bl, const PieceRan
 // `active` (may be null): [0] number of elements in the lists, [1] != 0 when a lane whose mask bit is clear carries a non-finite x.
 // The other n - active[0] lanes were dropped by the partition -- masked out of both gathers, or pointing outside the table (the
 // reference leaves that case unspecified, cuda.h:845-905; here it counts as masked out).  Their u is fma(0, x, 0): 0 for a finite
-// x, so they contribute map_op(0) to the reduction; NaN for an infinite or NaN x -- then the reference's result is NaN
+// x, so they contribute map_op(0) to the reduction -- or, next to a host-scalar addend c, fma(0, x, +-c) = +-c and map_op(+-c)
+// (`zero_u`); NaN for an infinite or NaN x -- then the reference's result is NaN
 // (dynamic.h:632-650 sums every lane) and so is this one (hsum, hprod; hmin / hmax skip NaNs here as everywhere: DESIGN section 5).
 template <typename T, int ROp>
-__device__ __forceinline__ T bucket_dropped_lanes(T r, size_t masked, bool nonfinite, int map_op) {
+__device__ __forceinline__ T bucket_dropped_lanes(T r, size_t masked, bool nonfinite, int map_op, T zero_u = T(0)) {
     using R = BucketReducer<ROp, T>;
     if (masked) {
-        const T f0 = unary_fused<T>(map_op, T(0));
+        const T f0 = unary_fused<T>(map_op, zero_u);
         if constexpr (ROp == EK_HSUM) {
             r = r + (T) masked * f0;
         } else if constexpr (ROp == EK_HPROD) {
@@ -312,7 +318,8 @@ __device__ __forceinline__ void finish_ticket_reset(uint32_t *__restrict__ ticke
 template <typename T, int ROp>
 __device__ __forceinline__ void bucket_finish(T block_result /* thread 0 */, T *__restrict__ partials, uint32_t *__restrict__ ticket,
                                               T *__restrict__ out, const uint32_t *__restrict__ active, size_t n, int map_op,
-                                              T *wave_part /* [kBucketWaves] shared */, uint32_t *__restrict__ counters = nullptr) {
+                                              T *wave_part /* [kBucketWaves] shared */, uint32_t *__restrict__ counters = nullptr,
+                                              T zero_u = T(0)) {
     using R = BucketReducer<ROp, T>;
     using Bits = std::conditional_t<sizeof(T) == 4, uint32_t, unsigned long long>;
     __shared__ uint32_t s_last;
@@ -349,7 +356,7 @@ __device__ __forceinline__ void bucket_finish(T block_result /* thread 0 */, T *
 #pragma unroll
         for (int d = 8; d >= 1; d >>= 1) v = R::combine(v, bucket_shfl_down(v, d));
         if (threadIdx.x == 0) {
-            out[0] = bucket_dropped_lanes<T, ROp>(v, active ? n - (size_t) active[0] : 0, active && active[1], map_op);
+            out[0] = bucket_dropped_lanes<T, ROp>(v, active ? n - (size_t) active[0] : 0, active && active[1], map_op, zero_u);
             finish_ticket_reset(ticket);
         }
     }
@@ -357,7 +364,8 @@ __device__ __forceinline__ void bucket_finish(T block_result /* thread 0 */, T *
 
 template <typename T, int ROp>
 __global__ __launch_bounds__(256) void k_bucket_reduce_final(T *__restrict__ out, const T *__restrict__ partials, unsigned count,
-                                                             const uint32_t *__restrict__ active, size_t n, int map_op) {
+                                                             const uint32_t *__restrict__ active, size_t n, int map_op,
+                                                             T zero_u = T(0)) {
     using R = BucketReducer<ROp, T>;
     __shared__ T wave_part[4];
     T v = R::identity();
@@ -368,7 +376,7 @@ __global__ __launch_bounds__(256) void k_bucket_reduce_final(T *__restrict__ out
     __syncthreads();
     if (threadIdx.x == 0) {
         T r = R::combine(R::combine(wave_part[0], wave_part[1]), R::combine(wave_part[2], wave_part[3]));
-        out[0] = bucket_dropped_lanes<T, ROp>(r, active ? n - (size_t) active[0] : 0, active && active[1], map_op);
+        out[0] = bucket_dropped_lanes<T, ROp>(r, active ? n - (size_t) active[0] : 0, active && active[1], map_op, zero_u);
     }
 }
 
@@ -609,6 +617,10 @@ struct Bucketed {
     int type = 0, index_type = 0, op = 0;
     size_t n = 0, table_size = 0;
     const void *table_a = nullptr, *table_c = nullptr;    // not owned: the caller keeps the tables alive and unchanged
+    // table_c == nullptr: the addend is a host scalar, uniform over the launch (ek_hip_bucketed_pair_create_scalar) -- or there is
+    // none (the product gather(A, idx) * x alone: staged as -0.0, see stage_pair_slice)
+    bool scalar_addend = false;
+    uint64_t addend_bits = 0;      // the scalar, bits of the element type
     int n_buckets = 0;
     unsigned max_pieces = 0;
     void *meta = nullptr;          // counts[n_buckets][blocks] | row_total | bucket_base | piece_prefix | reduce partials
@@ -651,6 +663,7 @@ struct Bucketed {
     template <typename T> BucketFinish<T> finish(void *out, int zero_op, bool reducing = true) {
         // (a ring block under a launch that reduces: its last workgroup clears the partition's counters -- from then on the block is clean)
         BucketFinish<T> f{ ticket, (T *) out, masked_ptr(), n, zero_op };
+        f.zero_u = dropped_u<T>();
         // (the block only counts as clean once that launch was really ENQUEUED FOR EXECUTION -- a launch recorded into a
         //  step graph may never run, a failed launch did not run: launched_reducing() below, called behind EK_LAUNCH_CHECK)
         if (reducing && meta_slot >= 0 && ticket) { f.counters = (uint32_t *) meta; meta_clean_pending = true; }
@@ -664,6 +677,20 @@ struct Bucketed {
     int flip_a() const { return op == EK_FNMADD || op == EK_FNMSUB || op == EK_NMULADD; }
     int flip_c() const { return op == EK_FMSUB || op == EK_FNMSUB || op == EK_MULSUB; }
     int two_roundings() const { return op == EK_MULADD || op == EK_MULSUB || op == EK_NMULADD; }
+    /// what stage_pair_slice stages as c without an addend table (flip_c() is applied to it there, like to a table entry)
+    template <typename T> T addend() const {
+        T c = T(-0.0);
+        if (scalar_addend) memcpy(&c, &addend_bits, sizeof(T));
+        return c;
+    }
+    /// u of a lane the partition dropped, for a finite x: fma(0, x, 0) = 0 with an addend table or none, fma(0, x, +-c) = +-c with a
+    /// host scalar (a zero c counts as +0 whatever its sign: the sum of +-0 * x and a zero depends on the sign of x)
+    template <typename T> T dropped_u() const {
+        if (!scalar_addend) return T(0);
+        const T c = addend<T>();
+        if (c == T(0)) return T(0);
+        return flip_c() ? -c : c;
+    }
     size_t bins() const { return (size_t) 1 << shift; }
     BucketLists lists() const { return BucketLists{ bucket_base, piece_prefix, base_part, glist_full, glist_part, n_buckets }; }
     ~Bucketed();

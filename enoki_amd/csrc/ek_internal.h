@@ -9,6 +9,7 @@
 #include <cstring>
 #include <type_traits>
 
+#define EK_HIP_LIBRARY 1        // (the library defines every entry point of the header, the optional ones included)
 #include "../../include/enoki_hip.h"
 
 namespace ek {

@@ -644,6 +644,12 @@ namespace detail {
 }
 
 namespace detail {
+    /// Backends that leave `op(gather(A, idx), x, c)` with a host scalar c unevaluated for a bucket-ordered consumer and offer a
+    /// scope in which they do not (HIPArray::ScalarAddendGuard; DiffArray: the scalar itself requires a gradient)
+    template <typename T, typename = void> struct has_scalar_addend_guard : std::false_type { using guard = void; };
+    template <typename T> struct has_scalar_addend_guard<T, std::void_t<typename T::ScalarAddendGuard>> : std::true_type {
+        using guard = typename T::ScalarAddendGuard;
+    };
     /// Backends that can run several scatter_adds through one index array in one pass (HIPArray::scatter_add_multi_)
     template <typename T, typename I, typename = void> struct has_scatter_add_multi : std::false_type { };
     template <typename T, typename I>

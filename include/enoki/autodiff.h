@@ -252,7 +252,17 @@ template <typename Type_> struct DiffArray : ArrayTag {
     // -----------------------------------------------------------------------------------------
     //  Differentiable vertical operations.  Edge weights follow autodiff.h:219-757.
     // -----------------------------------------------------------------------------------------
+    /// A host scalar that requires a gradient, next to a backend that would leave `gather * x + scalar` unevaluated for its
+    /// bucket-ordered path: that path does not cover a differentiable addend, the expression keeps its element-order kernels
+    static bool diff_scalar_(const DiffArray &a) {
+        if constexpr (Enabled && detail::has_scalar_addend_guard<Type>::value) return a.m_index != 0 && a.m_value.is_immediate();
+        else return false;
+    }
+    struct NoGuard { explicit NoGuard(bool) { } };
+    using ScalarGuard = std::conditional_t<detail::has_scalar_addend_guard<Type>::value, typename detail::has_scalar_addend_guard<Type>::guard, NoGuard>;
+
     DiffArray add_(const DiffArray &a) const {
+        [[maybe_unused]] ScalarGuard guard(diff_scalar_(*this) || diff_scalar_(a));
         Type result = m_value + a.m_value;
         Index idx = 0;
         if constexpr (Enabled) {
@@ -263,6 +273,7 @@ template <typename Type_> struct DiffArray : ArrayTag {
     }
 
     DiffArray sub_(const DiffArray &a) const {
+        [[maybe_unused]] ScalarGuard guard(diff_scalar_(*this) || diff_scalar_(a));
         Type result = m_value - a.m_value;
         Index idx = 0;
         if constexpr (Enabled) {
@@ -296,6 +307,7 @@ template <typename Type_> struct DiffArray : ArrayTag {
     }
 
     DiffArray fmadd_(const DiffArray &a, const DiffArray &b) const {
+        [[maybe_unused]] ScalarGuard guard(diff_scalar_(b));
         Type result = fmadd(m_value, a.m_value, b.m_value);
         Index idx = 0;
         if constexpr (Enabled) {
@@ -306,6 +318,7 @@ template <typename Type_> struct DiffArray : ArrayTag {
     }
 
     DiffArray fmsub_(const DiffArray &a, const DiffArray &b) const {
+        [[maybe_unused]] ScalarGuard guard(diff_scalar_(b));
         Type result = fmsub(m_value, a.m_value, b.m_value);
         Index idx = 0;
         if constexpr (Enabled) {
@@ -316,6 +329,7 @@ template <typename Type_> struct DiffArray : ArrayTag {
     }
 
     DiffArray fnmadd_(const DiffArray &a, const DiffArray &b) const {
+        [[maybe_unused]] ScalarGuard guard(diff_scalar_(b));
         Type result = fnmadd(m_value, a.m_value, b.m_value);
         Index idx = 0;
         if constexpr (Enabled) {
@@ -327,6 +341,7 @@ template <typename Type_> struct DiffArray : ArrayTag {
     }
 
     DiffArray fnmsub_(const DiffArray &a, const DiffArray &b) const {
+        [[maybe_unused]] ScalarGuard guard(diff_scalar_(b));
         Type result = fnmsub(m_value, a.m_value, b.m_value);
         Index idx = 0;
         if constexpr (Enabled) {

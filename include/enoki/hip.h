@@ -94,10 +94,17 @@ namespace detail {
             // EK_NMULADD: `gather(A, idx) * x + gather(B, idx)` written with operators, a product and a sum with a rounding each); a
             // horizontal reduction (through one fusable unary op) and the adjoint scatter_add of the ONE gather take it in bucket order
             // as it is; any other access runs the kernel that consumes the gather in place, as the eager product did.
+            // kind 2 with a HOST-SCALAR addend (table2 == nullptr, is_imm[2], bits of the element type in imm[2]; any op of the pair's
+            // seven):  op(table[index], arg0, c)  -- `fmadd(gather(A, idx), x, 0.5f)`, `gather(A, idx) * x + 0.5f`.  Same consumers as
+            // the product alone (ek_hip_bucketed_pair_create_scalar stages c into every {a, c} record); any other access runs the
+            // element-order kernels the eager expression ran: the gather consumed in place by the fma, or by the product with the
+            // sum behind it.
             int arity = 0;
             uint64_t imm[3] = { 0, 0, 0 };
             bool is_imm[3] = { false, false, false };
             HIPBuffer *operand_buf(int k) const { return k == 0 ? table : k == 1 ? arg0 : table2; }
+            bool scalar_addend() const { return kind == 2 && !table2 && is_imm[2]; }
+            bool product_alone() const { return kind == 2 && !table2 && !is_imm[2]; }
         };
         Deferred *deferred = nullptr;
         std::vector<HIPBuffer *> readers;      // deferred nodes whose table / source is THIS buffer (not owning)
@@ -112,6 +119,7 @@ namespace detail {
             bool defer = true;
             bool scatter_alias = false;      // hip_set_scatter_aliasing(): user-level scatters write in place through shared handles
             int sweeps = 0;                  // > 0 while a Tape sweep runs (its buffers are shared as VALUES: always copy on write)
+            int scalar_addend_off = 0;       // > 0 inside a HIPArray::ScalarAddendGuard: no kind-2 node with a host-scalar addend
         };
         static Shared &shared() {
             void **slot = ek_hip_binding_slot();
@@ -259,6 +267,7 @@ namespace detail {
                                    "evaluated in ELEMENT order -- its consumer is not a horizontal reduction (directly or through one "
                                    "fusable unary op) nor the adjoint scatter_add of its gathers, or a source is about to be written, or a "
                                    "step graph is being captured, or deterministic mode is on");
+            if (d->scalar_addend()) { force_scalar_addend(); return; }
             if (!d->table2) { force_gathered_product(); return; }
             void *p = nullptr;
             hip_check(ek_hip_malloc((size ? size : 1) * d->elem_size, &p), "HIPArray (deferred fma of gathers)");
@@ -285,7 +294,16 @@ namespace detail {
         /// The bucket partition of a kind-2 node (built on first use); nullptr when the library does not cover the shape
         ek_hip_bucketed *bucketed(unsigned hints = 0) {
             Deferred *d = deferred;
-            if (!d->bucketed) {
+            if (!d->bucketed && d->scalar_addend()) {
+                // (EK_OPTIONAL in enoki_hip.h: a C ABI that predates the entry, or a host stand-in of it, leaves the address null --
+                //  "shape not covered", the expression runs in element order with the same bits)
+                if (!&ek_hip_bucketed_pair_create_scalar) return nullptr;
+                int rc = ek_hip_bucketed_pair_create_scalar(d->type, d->index_type, d->op, d->table->ptr, d->imm[2], d->table->size, d->arg0->ptr,
+                                                            d->index->ptr, d->mask ? (const uint8_t *) d->mask->ptr : nullptr, size, hints,
+                                                            &d->bucketed);
+                if (rc == EK_ERR_UNSUPPORTED) return nullptr;
+                hip_check(rc, "HIPArray (bucket partition)");
+            } else if (!d->bucketed) {
                 int rc = ek_hip_bucketed_pair_create_masked(d->type, d->index_type, d->op, d->table->ptr, d->table2 ? d->table2->ptr : nullptr, d->table->size,
                                                             d->arg0->ptr, d->index->ptr, d->mask ? (const uint8_t *) d->mask->ptr : nullptr,
                                                             size, hints, &d->bucketed);
@@ -327,6 +345,35 @@ namespace detail {
             if (ek_hip_map_gathered(2, EK_MUL, d->type, p, po, pg, size) != EK_OK) {
                 ek_hip_free(p);
                 hip_raise("HIPArray (deferred product of a gather)");
+            }
+            ptr = p;
+            drop_deferred();
+        }
+
+        /// kind 2 with a host-scalar addend, element order: the fma family consumes the gather in place (one kernel); the operator
+        /// forms are the product that consumes the gather and the sum with the scalar behind it, in place -- the kernels and the
+        /// bits of the eager expression
+        void force_scalar_addend() {
+            Deferred *d = deferred;
+            void *p = nullptr;
+            hip_check(ek_hip_malloc((size ? size : 1) * d->elem_size, &p), "HIPArray (deferred fma of a gather and a scalar)");
+            ek_gathered g = gathered();
+            ek_operand x{ d->arg0->ptr, 0, d->arg0->size }, c{ nullptr, d->imm[2], 1 };
+            const ek_gathered *pg[3] = { &g, nullptr, nullptr };
+            const ek_operand *po[3] = { nullptr, &x, &c };
+            int rc;
+            if (d->op == EK_MULADD || d->op == EK_MULSUB || d->op == EK_NMULADD) {
+                rc = ek_hip_map_gathered(2, EK_MUL, d->type, p, po, pg, size);
+                ek_operand prod{ p, 0, size };
+                if (rc == EK_OK)
+                    rc = d->op == EK_NMULADD ? ek_hip_binary(EK_SUB, d->type, p, &c, &prod, size)
+                                             : ek_hip_binary(d->op == EK_MULADD ? EK_ADD : EK_SUB, d->type, p, &prod, &c, size);
+            } else {
+                rc = ek_hip_map_gathered(3, d->op, d->type, p, po, pg, size);
+            }
+            if (rc != EK_OK) {
+                ek_hip_free(p);
+                hip_raise("HIPArray (deferred fma of a gather and a scalar)");
             }
             ptr = p;
             drop_deferred();
@@ -981,7 +1028,7 @@ template <typename Value_> struct HIPArray : ArrayTag {
     bool paired_() const { return m_buf && m_buf->deferred && m_buf->deferred->kind == 2; }
 
     /// gather(A, idx) * x that has not run yet (kind 2 without an addend table, see detail::HIPBuffer)
-    bool gathered_product_() const { return m_buf && m_buf->deferred && m_buf->deferred->kind == 2 && !m_buf->deferred->table2; }
+    bool gathered_product_() const { return m_buf && m_buf->deferred && m_buf->deferred->product_alone(); }
 
     /// g * x with g an unevaluated gather and x an evaluated array of the same length: left unevaluated (kind 2 without an addend)
     /// when the library's bucket-ordered path covers the shape.  Invalid array: not that shape -- the caller consumes the gather
@@ -1031,6 +1078,73 @@ template <typename Value_> struct HIPArray : ArrayTag {
             x.m_buf = p->arg0;
             x.m_buf->ref_count++;
             r = defer_pair_fma_(form, *this, x, gc, n);
+        }
+        return r;
+    }
+
+    /// hip_set_log_level(2): why an addend that is not a host scalar keeps `gather * x + addend` out of bucket order
+    static void note_plain_addend_(const char *shape, const HIPArray &c, size_t n) {
+        const char *why = !c.m_buf ? "the addend is not initialized"
+            : c.m_buf->deferred ? "the addend is itself unevaluated (a unary map, an arithmetic node, or a gather that does not share index array, mask and table size with the product's)"
+            : c.m_buf->size == 1 ? "the addend is a size-1 DEVICE array, not a host scalar (its value is not known on the host)"
+            : c.m_buf->size == n ? "the addend is an n-element array (only a gather through the same index array or a host scalar stays in bucket order)"
+            : "the addend has another length";
+        detail::hip_note_element_order(shape, why);
+    }
+
+    /// While an armed one is alive, a host-scalar addend next to a gathered product does not make a kind-2 node.  DiffArray holds one
+    /// around an addend that REQUIRES A GRADIENT: that shape is outside the bucket-ordered path and keeps its element-order kernels.
+    struct ScalarAddendGuard {
+        explicit ScalarAddendGuard(bool armed) : armed(armed) { if (armed) ++detail::HIPBuffer::shared().scalar_addend_off; }
+        ~ScalarAddendGuard() { if (armed) --detail::HIPBuffer::shared().scalar_addend_off; }
+        ScalarAddendGuard(const ScalarAddendGuard &) = delete;
+        ScalarAddendGuard &operator=(const ScalarAddendGuard &) = delete;
+        bool armed;
+    };
+
+    /// op(gather(A, idx[, mask]), x, c) with c a host scalar (fma family or a product-then-sum form), left unevaluated as the kind-2
+    /// node with a scalar addend when the library's bucket-ordered path covers the shape -- x an array under the conditions of
+    /// defer_gathered_product_().  `g`: the unevaluated gather, or the unevaluated product gather * x (then `x` is not looked at).
+    /// Invalid array: not that shape.
+    static HIPArray defer_scalar_addend_(int op, const HIPArray &g, const HIPArray &x, const HIPArray &c, size_t n) {
+        HIPArray r;
+        if constexpr (IsFloat) {
+            const char *shape = "fma(gather(A, idx), x, c) with a host scalar c";
+            const auto *p = g.m_buf->deferred;
+            detail::HIPBuffer *xb = p->kind == 2 ? p->arg0 : x.m_buf;
+            if (!detail::hip_defer_gather_flag() || !c.m_is_imm || g.m_buf->size != n) return r;
+            if (detail::HIPBuffer::shared().scalar_addend_off) { detail::hip_note_element_order(shape, "the scalar addend requires a gradient"); return r; }
+            if (p->kind != 2) {
+                if (x.m_is_imm || !xb || xb->size != n) { detail::hip_note_element_order(shape, "x is a scalar / of another length"); return r; }
+                if (!xb->owned || xb->exported) { detail::hip_note_element_order(shape, "x is a view of foreign memory or has a zero-copy export (an external writer could change it)"); return r; }
+                if (xb->deferred) { detail::hip_note_element_order(shape, "x is itself unevaluated"); return r; }
+                if (p->mask && sizeof(Value) != 4) { detail::hip_note_element_order(shape, "masked gathers of 8-byte elements"); return r; }
+                if (!ek_hip_bucketed_applicable(Type, p->index_type, p->table->size, n)) {
+                    detail::hip_note_element_order(shape, "the library does not cover the shape (fewer than 2^18 lookups, a table within one bucket or beyond "
+                                                          "64 slices, deterministic mode, ENOKI_HIP_BUCKET_ORDERED=0)");
+                    return r;
+                }
+            }
+            auto *d = new typename detail::HIPBuffer::Deferred{ p->table, p->index, p->mask, Type, p->index_type, sizeof(Value),
+                                                                false, 2, nullptr };
+            d->arg0 = xb;
+            d->op = op;
+            d->is_imm[2] = true;
+            d->imm[2] = imm_bits(c.m_imm);
+            r.m_buf = new detail::HIPBuffer();
+            r.m_buf->size = n;
+            r.m_buf->deferred = d;
+            r.m_buf->pending_link();
+            detail::HIPBuffer *seen[4] = { nullptr, nullptr, nullptr, nullptr };
+            int k = 0;
+            for (detail::HIPBuffer *src : { d->table, d->index, d->arg0, d->mask }) {
+                if (!src) continue;
+                src->ref_count++;
+                bool dup = false;
+                for (int j = 0; j < k; ++j) dup = dup || seen[j] == src;
+                if (!dup) { src->readers.push_back(r.m_buf); seen[k++] = src; }
+            }
+            if (p->kind != 2) g.m_buf->deferred->consumed = true;
         }
         return r;
     }
@@ -1509,8 +1623,20 @@ template <typename Value_> struct HIPArray : ArrayTag {
         const auto *d = u->deferred;
         if (d->index != index.m_buf || d->index_type != Index::Type || u->size != index.m_buf->size || d->mask != mask_buf) return false;
         for (size_t c = 0; c < count; ++c) {
-            if (weighted[c] && (weights[c]->m_is_imm || weights[c]->m_buf != d->arg0)) return false;
             if (targets[c]->size() != d->table->size) return false;
+            if (!weighted[c] || (!weights[c]->m_is_imm && weights[c]->m_buf == d->arg0)) continue;
+            // the -x that fnmadd / fnmsub record as the weight of their first operand, still an unevaluated neg(x): the stream's
+            // scale takes the sign (exact).  Only next to a scalar addend: a pair of gathers keeps the path it has (its fnmadd /
+            // fnmsub adjoint runs in element order, as before).  Not covered either way: every value stream a host scalar
+            // (`hsum(fnmadd(..))` itself, no map in between) -- u is then looked for among the readers of the WEIGHT's buffer
+            // above, which for -x is the neg node's, not x's: no u, element order.
+            const HIPArray &w = *weights[c];
+            if (!d->scalar_addend() || !w.mapped_() || w.m_buf->deferred->index_type != EK_NEG || w.m_buf->deferred->scaled ||
+                w.m_buf->deferred->table != d->arg0)
+                return false;
+            Value sc;
+            memcpy(&sc, &scale[c], sizeof(Value));
+            scale[c] = imm_bits(Value(-sc));
         }
         // writers first: a target that aliases one of u's sources evaluates u (and drops its partition) right here.  A target
         // that is a pending zeros node held by nobody else (the fresh gradient buffer of the sweep) is not memset: the fold
@@ -1623,7 +1749,7 @@ template <typename Value_> struct HIPArray : ArrayTag {
             case 1: return std::string("unevaluated unary op ") + std::to_string(d->index_type) + (d->scaled ? " times a host scalar" : "") + ", " + n +
                            ": reductions and scatter_add value streams apply it while loading; source " +
                            (d->table->deferred ? "unevaluated (kind " + std::to_string(d->table->deferred->kind) + ")" : "evaluated");
-            case 2: return "unevaluated " + std::string(!d->table2 ? "product of a gather with an array" : d->op >= EK_MULADD ? "product-then-sum of two gathers through one index array" : "fma of two gathers through one index array") + " (K = " +
+            case 2: return "unevaluated " + std::string(d->scalar_addend() ? (d->op >= EK_MULADD ? "product of a gather with an array, then sum with a host scalar" : "fma of a gather, an array and a host scalar") : !d->table2 ? "product of a gather with an array" : d->op >= EK_MULADD ? "product-then-sum of two gathers through one index array" : "fma of two gathers through one index array") + " (K = " +
                            std::to_string(d->table->size) + ", " + n + "): BUCKET ORDER possible -- a horizontal reduction (directly or through one fusable "
                            "unary op) and the adjoint scatter_add of the gathers stay in bucket order; any other access evaluates it in element order" +
                            (d->bucketed ? "; partition built" : "");
@@ -1858,6 +1984,19 @@ private:
             bool d[3] = { false, false, false };
             for (int k = 0; k < arity; ++k) d[k] = x[k]->deferred_() && x[k]->m_buf->size == n;
             if (d[0] && d[1]) d[1] = false;                                  // one gathered factor per product
+            if (arity == 3 && (d[0] || d[1]) && !d[2]) {
+                // a gathered factor next to a HOST-SCALAR addend (`fmadd(gather(A, idx), x, 0.5f)`): stays unevaluated for bucket order
+                const HIPArray &c = *x[2];
+                const char *shape = "fma(gather(A, idx), x, c)";
+                if (c.m_is_imm) {
+                    if (HIPArray r = defer_scalar_addend_(op, *x[d[0] ? 0 : 1], *x[d[0] ? 1 : 0], c, n); r.valid()) {
+                        result = std::move(r);
+                        return true;
+                    }
+                } else {
+                    note_plain_addend_(shape, c, n);
+                }
+            }
             if (arity == 3 && d[2] && (d[0] || d[1])) {
                 // a gathered factor AND a gathered addend: one 8-byte lookup when they share index, mask and table size
                 const auto *p = x[d[0] ? 0 : 1]->m_buf->deferred, *q = x[2]->m_buf->deferred;
@@ -1941,6 +2080,18 @@ private:
                 HIPArray r = gathered_product_() ? gathered_product_plus_(op == EK_ADD ? EK_MULADD : EK_MULSUB, b, n)
                                                  : b.gathered_product_plus_(op == EK_ADD ? EK_MULADD : EK_NMULADD, *this, n);
                 if (r.valid()) return r;
+            }
+            // `gather(A, idx) * x + c`, `c - gather(A, idx) * x`, ... with a host scalar c: the unevaluated product becomes the node of
+            // the whole expression (a product and a sum with a rounding each)
+            if ((op == EK_ADD || op == EK_SUB) && (gathered_product_() || b.gathered_product_())) {
+                const HIPArray &pr = gathered_product_() ? *this : b, &c = gathered_product_() ? b : *this;
+                const char *shape = "gather(A, idx) * x +- c";
+                if (c.m_is_imm && pr.m_buf->size == n) {
+                    const int form = op == EK_ADD ? EK_MULADD : (&pr == this ? EK_MULSUB : EK_NMULADD);
+                    if (HIPArray r = defer_scalar_addend_(form, pr, pr, c, n); r.valid()) return r;
+                } else if (!c.m_is_imm) {
+                    note_plain_addend_(shape, c, n);
+                }
             }
         }
         if ((op == EK_ADD || op == EK_SUB || op == EK_MUL) && (deferred_() || b.deferred_())) {

@@ -35,6 +35,14 @@ extern "C" {
 #else
 #  define EK_API __attribute__((visibility("default")))
 #endif
+/* An entry point that a caller can do without: declared WEAK for everybody but the library itself, so that code compiled
+ * against this header still links and loads against a C ABI that predates the entry (or a host stand-in of the ABI) -- the
+ * function's address is then null, and the caller asks before it calls. */
+#if defined(_WIN32) || defined(EK_HIP_LIBRARY)
+#  define EK_OPTIONAL
+#else
+#  define EK_OPTIONAL __attribute__((weak))
+#endif
 
 /* Element types -- the subset of EnokiType (src/cuda/common.cuh:25-40) on the hot path. */
 typedef enum {
@@ -313,6 +321,19 @@ EK_API int ek_hip_bucketed_pair_create_hinted(int type, int index_type, int op, 
  * the slices of a large table alike.
  * mask: n bytes or NULL; 4-byte element types only. */
 EK_API int ek_hip_bucketed_pair_create_masked(int type, int index_type, int op, const void *table_a, const void *table_c,
+                                              size_t table_size, const void *x, const void *index, const uint8_t *mask, size_t n,
+                                              unsigned hints, ek_hip_bucketed **out);
+/* create_scalar: u = op(A[index], x, c) with ONE host scalar c in place of the addend table -- `fmadd(gather(A, idx), x, 0.5f)`,
+ * `gather(A, idx) * x + 0.5f`.  addend_bits: c as bits of the element type.  All seven ops (the fma family, EK_MULADD / EK_MULSUB /
+ * EK_NMULADD); any other op: EK_ERR_INVALID.  The kernels are the pair's: c is staged into every {a, c} record of a bucket's
+ * table slice (with the sign of the op, like a table entry), so every call on the object behaves as with a table filled with c --
+ * except for the lanes the partition drops (mask bit clear, index outside the table): only the gather is masked, their u is
+ * fma(0, x, +-c) = +-c for a finite x (-c for EK_FMSUB / EK_FNMSUB / EK_MULSUB), and a reduction counts map_op(+-c) for each
+ * (a zero c: map_op(+0)); a non-finite x there makes hsum / hprod NaN as above.  They scatter nothing.  A NaN or infinite c takes
+ * the fixed-point adjoint sums (EK_BUCKETED_HINT_BOUNDED) down the lock path like a non-finite table entry.  mask, hints, shapes and
+ * return codes as for create_masked.  EK_OPTIONAL: enoki/hip.h asks for the entry's address first and evaluates in element
+ * order without it. */
+EK_API EK_OPTIONAL int ek_hip_bucketed_pair_create_scalar(int type, int index_type, int op, const void *table_a, uint64_t addend_bits,
                                               size_t table_size, const void *x, const void *index, const uint8_t *mask, size_t n,
                                               unsigned hints, ek_hip_bucketed **out);
 EK_API int ek_hip_bucketed_reduce(ek_hip_bucketed *b, int reduce_op, int map_op, void *out, int keep_values, int keep_op);
