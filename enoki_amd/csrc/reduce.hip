@@ -661,6 +661,11 @@ int ek_hip_reduce_chain(int reduce_op, int type, void *out, const ek_chain *chai
     if (int rc = ensure_init()) return rc;
     if (!out) return fail(EK_ERR_INVALID, "ek_hip_reduce_chain(): null pointer");
     if (n == 0) return fail(EK_ERR_INVALID, "ek_hip_reduce_chain(): empty input");
+    if (n == 1 && (type == EK_F32 || type == EK_F64)) {
+        // like ek_hip_reduce(), which copies a single element: the term itself, not identity (+) term (0 + -0.0 is +0.0)
+        if (reduce_op < 0 || reduce_op >= EK_REDUCE_COUNT) return fail(EK_ERR_INVALID, "ek_hip_reduce_chain(): unknown op %d", reduce_op);
+        return ek_hip_map_chain(type, out, chain, 1);
+    }
     switch (type) {
         case EK_F32: return chain_reduce<float>(reduce_op, out, chain, n);
         case EK_F64: return chain_reduce<double>(reduce_op, out, chain, n);
@@ -694,6 +699,11 @@ int ek_hip_reduce_map(int op, int map_op, int type, void *out, const void *in, s
     if (!out || !in) return fail(EK_ERR_INVALID, "ek_hip_reduce_map(): null pointer");
     if (n == 0) return fail(EK_ERR_INVALID, "ek_hip_reduce_map(): empty input");
     if (!unary_chainable(map_op)) return fail(EK_ERR_UNSUPPORTED, "ek_hip_reduce_map(): op %d cannot be applied on load", map_op);
+    if (n == 1 && (type == EK_F32 || type == EK_F64)) {       // the mapped element itself, as ek_hip_reduce() copies a single element
+        if (op < 0 || op >= EK_REDUCE_COUNT) return fail(EK_ERR_INVALID, "ek_hip_reduce_map(): unknown op %d", op);
+        const ek_operand a{ in, 0, 1 };
+        return ek_hip_unary(map_op, type, out, &a, 1);
+    }
     switch (type) {
         case EK_F32: return reduce_map_dispatch<float>(op, map_op, out, in, n);
         case EK_F64: return reduce_map_dispatch<double>(op, map_op, out, in, n);
@@ -705,6 +715,8 @@ int ek_hip_hsum_safe_mul(int type, void *out, const ek_operand *w, const ek_oper
     if (int rc = ensure_init()) return rc;
     if (!out) return fail(EK_ERR_INVALID, "ek_hip_hsum_safe_mul(): null output pointer");
     if (n == 0) return ek_hip_fill(type, out, 0, 1);
+    if (n == 1 && (type == EK_F32 || type == EK_F64))          // the product itself (it may be -0.0), as ek_hip_reduce() copies a single element
+        return ek_hip_binary(EK_SAFE_MUL, type, out, w, g, 1);
     if (type == EK_F32) {
         SafeMulLoader<float> ld;
         if (int rc = make_arg<float>(w, n, ld.w, "ek_hip_hsum_safe_mul")) return rc;
