@@ -46,8 +46,8 @@ EXPORTS = [
     "ek_hip_graph_launch_count", "ek_hip_graph_destroy", "ek_hip_sort_pairs", "ek_hip_reduce_map", "ek_hip_reduce_chain", "ek_hip_map_chain", "ek_hip_map_chain_product", "ek_hip_partition_class_state", "ek_hip_scatter_add_multi_map", "ek_hip_binding_slot",
     "ek_hip_dist_unique_id", "ek_hip_dist_init", "ek_hip_dist_world", "ek_hip_dist_shard_range", "ek_hip_dist_all_reduce",
     "ek_hip_dist_reduce_scatter", "ek_hip_dist_all_gather", "ek_hip_dist_finalize", "ek_hip_dist_rccl_path",
-    "ek_hip_bucketed_applicable", "ek_hip_bucketed_pair_create", "ek_hip_bucketed_pair_create_hinted", "ek_hip_bucketed_pair_create_masked", "ek_hip_bucketed_pair_create_scalar", "ek_hip_bucketed_reduce", "ek_hip_bucketed_scatter_add", "ek_hip_bucketed_scatter_add_scaled", "ek_hip_bucketed_early_pair",
-    "ek_hip_bucketed_destroy", "ek_hip_index_partition_create", "ek_hip_index_partition_get", "ek_hip_index_partition_destroy", "ek_hip_gather_address",
+    "ek_hip_bucketed_applicable", "ek_hip_bucketed_pair_create", "ek_hip_bucketed_pair_create_hinted", "ek_hip_bucketed_pair_create_masked", "ek_hip_bucketed_pair_create_scalar", "ek_hip_bucketed_pair_create_scalar_device", "ek_hip_bucketed_addend_adjoint", "ek_hip_bucketed_reduce", "ek_hip_bucketed_scatter_add", "ek_hip_bucketed_scatter_add_scaled", "ek_hip_bucketed_early_pair",
+    "ek_hip_bucketed_piece_counts", "ek_hip_bucketed_destroy", "ek_hip_index_partition_create", "ek_hip_index_partition_get", "ek_hip_index_partition_destroy", "ek_hip_gather_address",
 ]
 
 
@@ -499,7 +499,7 @@ def psum(a):
 class Bucketed:
     """u = op(A[index], x, C[index]) kept in bucket order (ek_hip_bucketed_*): reductions over map(u) and the adjoint
     scatter_add of the two gathers without a lookup that leaves the CU.  Keeps A, C alive; x and index may be dropped.
-    C may be a python float: the host-scalar addend of `fmadd(gather(A, idx), x, c)`."""
+    C may be a python float: the host-scalar addend of `fmadd(gather(A, idx), x, c)` -- or a Buf of ONE element: that scalar on the device."""
 
     HINT_ADJOINT = 1
     HINT_BOUNDED = 2
@@ -507,6 +507,15 @@ class Bucketed:
     def __init__(self, op, A, x, C, index, hints=0, mask=None):
         self.A, self.C, self.dtype, self.K = A, C, A.dtype, A.n
         h = ctypes.c_void_p()
+        if isinstance(C, Buf) and C.n == 1 and A.n != 1:
+            # a size-1 device array as the scalar addend (ek_hip_bucketed_pair_create_scalar_device): read on the stream, never by the host
+            code = TERNARY[op] if isinstance(op, str) else int(op)
+            check(lib.ek_hip_bucketed_pair_create_scalar_device(A.ek, index.ek, code, ctypes.c_void_p(A.ptr), ctypes.c_void_p(C.ptr),
+                                                                ctypes.c_size_t(A.n), ctypes.c_void_p(x.ptr), ctypes.c_void_p(index.ptr),
+                                                                ctypes.c_void_p(mask.ptr if mask is not None else None),
+                                                                ctypes.c_size_t(index.n), ctypes.c_uint(hints), ctypes.byref(h)))
+            self.handle = h
+            return
         if not isinstance(C, Buf):
             # a host scalar in place of the addend table (ek_hip_bucketed_pair_create_scalar); op may also be a raw op code
             code = TERNARY[op] if isinstance(op, str) else int(op)
@@ -534,6 +543,14 @@ class Bucketed:
                                          UNARY[keep_op or "copy"]))
         return out
 
+    def addend_adjoint(self, map_op=None, scale=1.0):
+        """scale * sum over ALL lanes of map_op(u): the gradient of the scalar addend (ek_hip_bucketed_addend_adjoint); the sign of
+        du/dc is the caller's.  Raises EnokiHipError (EK_ERR_INVALID) for an object without a scalar addend."""
+        out = Buf(self.dtype, 1)
+        check(lib.ek_hip_bucketed_addend_adjoint(self.handle, UNARY[map_op or "copy"], ctypes.c_uint64(_imm_bits(scale, self.dtype)),
+                                                 ctypes.c_void_p(out.ptr)))
+        return out
+
     def scatter_add(self, targets, streams, fresh=None, scales=None):
         """streams[c] = (map_op name | None for a constant, constant value, weighted by x?); fresh[c]: table c holds no data
         yet, its sums are written instead of added; scales[c]: host scalar factor on stream c"""
@@ -549,6 +566,12 @@ class Bucketed:
             check(lib.ek_hip_bucketed_scatter_add_scaled(self.handle, count, bases, from_u, ops, imm, wt, fr, sc))
         else:
             check(lib.ek_hip_bucketed_scatter_add(self.handle, count, bases, from_u, ops, imm, wt, fr))
+
+    def piece_counts(self):
+        """(pieces that exist, most pieces of any one bucket) -- ek_hip_bucketed_piece_counts; synchronises"""
+        total, largest = ctypes.c_uint32(), ctypes.c_uint32()
+        check(lib.ek_hip_bucketed_piece_counts(self.handle, ctypes.byref(total), ctypes.byref(largest)))
+        return total.value, largest.value
 
     def destroy(self):
         if self.handle:

@@ -963,6 +963,175 @@ __global__ __launch_bounds__(256) void k_fold_fixed_pieces(FoldTargets<float, C>
     }
 }
 
+// ---- the adjoint of a SCALAR addend from the early sums ---------------------------------------------------------------------------
+// Plane 0 of the per-piece tables of the forward + adjoint kernel holds, per table entry, the sum of keep_op(u) over the entry's
+// lanes: its sum over all entries (plus what the dropped lanes contribute) is d/dc of hsum(map_op(u)) for u = a x +- c -- one small
+// fold over data that is already in memory.  Every lane forms the values of four consecutive entries exactly as the scatter_add
+// fold would write them into a fresh table (fixed-point pieces added as integers and converted once, float pieces on top), adds
+// them in entry order, the workgroup adds its lanes by wave shuffles, and the LAST workgroup to arrive (finish ticket) adds the
+// workgroups' partials in index order: the order of all additions is a function of the entry index alone -- no fp atomics.
+/// Entries [k0, k0 + lim) of ONE plane of the fixed-point per-piece tables (`partials`: the plane's first slot; pieces [p0, p1) of the
+/// entries' bucket): v[j] = (the integer sum, converted once) * back + the float pieces' sum -- the arithmetic of k_fold_fixed_pieces,
+/// statement for statement (that kernel keeps its own copy: its code is the headline step's and does not move).
+__device__ __forceinline__ void fixed_piece_sums_at(const long long *__restrict__ partials, const uint32_t *__restrict__ piece_mode,
+                                                    const uint32_t p0, const uint32_t p1, const uint32_t local, const int lim,
+                                                    const int shift, const float back, float (&v)[kFoldPerLane]) {
+    // (128 bits: a piece's sums stay below 2^62 by the choice of the scale, a skewed bucket of many pieces may not)
+    unsigned long long ilo[kFoldPerLane];
+    long long ihi[kFoldPerLane];
+    float fsum[kFoldPerLane];
+#pragma unroll
+    for (int j = 0; j < kFoldPerLane; ++j) { ilo[j] = 0; ihi[j] = 0; fsum[j] = 0.f; }
+    if (p1 - p0 == 1u) {
+        // a bucket that is one piece wrote floats whatever it ran under (bucketed_early.hip): no mode to wait for, a quarter of the bytes
+        const float *slotf = reinterpret_cast<const float *>(partials + ((size_t) p0 << shift));
+#pragma unroll
+        for (int j = 0; j < kFoldPerLane; ++j) if (j < lim) fsum[j] = __builtin_nontemporal_load(slotf + local + j);
+    } else
+    for (uint32_t p = p0; p < p1; ++p) {
+        // (mode and sums requested together: the 64-bit words of a slot can be read whatever the piece wrote into it)
+        const long long *slot = partials + ((size_t) p << shift);
+        const uint32_t mode = piece_mode[p];
+        long long w[kFoldPerLane];
+#pragma unroll
+        for (int j = 0; j < kFoldPerLane; ++j) w[j] = j < lim ? __builtin_nontemporal_load(slot + local + j) : 0ll;
+        if (mode == 0u) {
+#pragma unroll
+            for (int j = 0; j < kFoldPerLane; ++j) {
+                const unsigned long long before = ilo[j];
+                ilo[j] += (unsigned long long) w[j];
+                ihi[j] += (w[j] >> 63) + (ilo[j] < before ? 1 : 0);
+            }
+        } else {
+            const float *slotf = reinterpret_cast<const float *>(slot);
+#pragma unroll
+            for (int j = 0; j < kFoldPerLane; ++j) if (j < lim) fsum[j] += slotf[local + j];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < kFoldPerLane; ++j) {
+        // (one conversion of the exact integer: the same integer gives the same float whatever the pieces were)
+        const bool narrow = ihi[j] == ((long long) ilo[j] >> 63);
+        const float s = narrow ? (float) (long long) ilo[j] : (float) ((double) ihi[j] * 18446744073709551616.0 + (double) ilo[j]);
+        v[j] = s * back + fsum[j];
+    }
+}
+
+
+template <typename T>
+__device__ __forceinline__ T addend_adjoint_block_sum(T v, T *wave_part /* [4] shared */) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += bucket_shfl_down(v, d);
+    __syncthreads();                                  // (wave_part may still be read by an earlier round)
+    if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (wave_part[0] + wave_part[1]) + (wave_part[2] + wave_part[3]);
+}
+
+/// the workgroups' partials in index order, the dropped lanes' map_op(+-c) each (NaN: one of them carried a non-finite x), the factor
+template <typename T>
+__device__ __forceinline__ void addend_adjoint_finish(T *__restrict__ out, const T *__restrict__ block_partials, unsigned count,
+                                                      const uint32_t *__restrict__ active, size_t n, int map_op, T zero_u, T scale,
+                                                      T *wave_part) {
+    using Bits = std::conditional_t<sizeof(T) == 4, uint32_t, unsigned long long>;
+    T v = T(0);
+    for (unsigned i = threadIdx.x; i < count; i += 256) {
+        const Bits b = __hip_atomic_load(reinterpret_cast<const Bits *>(block_partials) + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        T p;
+        __builtin_memcpy(&p, &b, sizeof(T));
+        v += p;
+    }
+    const T r = addend_adjoint_block_sum(v, wave_part);
+    if (threadIdx.x == 0) {
+        const T all = bucket_dropped_lanes<T, EK_HSUM>(r, active ? n - (size_t) active[0] : 0, active && active[1], map_op, zero_u);
+        out[0] = scale != T(1) ? all * scale : all;
+    }
+}
+
+template <typename T, bool Fixed>
+__global__ __launch_bounds__(256) void k_addend_adjoint_fold(T *__restrict__ out, T *__restrict__ block_partials, uint32_t *__restrict__ ticket,
+                                                             const void *__restrict__ plane0, const uint32_t *__restrict__ piece_mode,
+                                                             const uint32_t *__restrict__ piece_prefix, size_t table_size, int shift,
+                                                             const uint32_t *__restrict__ xmax_bits, int S0,
+                                                             const uint32_t *__restrict__ active, size_t n, int map_op, T zero_u, T scale) {
+    using Bits = std::conditional_t<sizeof(T) == 4, uint32_t, unsigned long long>;
+    __shared__ T wave_part[4];
+    __shared__ uint32_t s_last;
+    const size_t k0 = ((size_t) blockIdx.x * 256 + threadIdx.x) * kFoldPerLane;
+    T v = T(0);
+    if (k0 < table_size) {
+        const uint32_t b = (uint32_t) (k0 >> shift), local = (uint32_t) (k0 & (((size_t) 1 << shift) - 1));
+        const uint32_t p0 = piece_prefix[b], p1 = piece_prefix[b + 1];
+        const int lim = (int) (table_size - k0 < (size_t) kFoldPerLane ? table_size - k0 : (size_t) kFoldPerLane);
+        T e[kFoldPerLane];
+        if constexpr (Fixed) {
+            fixed_piece_sums_at((const long long *) plane0, piece_mode, p0, p1, local, lim, shift, fixed_scale(S0, xmax_bits[0], false).back, e);
+        } else {
+            const T *partials = (const T *) plane0;
+#pragma unroll
+            for (int j = 0; j < kFoldPerLane; ++j) e[j] = T(0);
+            for (uint32_t p = p0; p < p1; ++p) {
+                const T *slot = partials + ((size_t) p << shift) + local;
+#pragma unroll
+                for (int j = 0; j < kFoldPerLane; ++j) if (j < lim) e[j] += __builtin_nontemporal_load(slot + j);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kFoldPerLane; ++j) if (j < lim) v += T(0) + e[j];      // (0 + e: the entry of a fresh table, as the fold writes it)
+    }
+    const T r = addend_adjoint_block_sum(v, wave_part);
+    if (threadIdx.x == 0) {
+        Bits bits;
+        __builtin_memcpy(&bits, &r, sizeof(T));
+        __hip_atomic_store(reinterpret_cast<Bits *>(block_partials) + blockIdx.x, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = ticket && finish_ticket(ticket);
+    }
+    __syncthreads();
+    if (!s_last) return;
+    addend_adjoint_finish<T>(out, block_partials, gridDim.x, active, n, map_op, zero_u, scale, wave_part);
+    if (threadIdx.x == 0) finish_ticket_reset(ticket);
+}
+
+/// objects without a finish ticket (8-byte element types): the last step as a launch of its own
+template <typename T>
+__global__ __launch_bounds__(256) void k_addend_adjoint_final(T *__restrict__ out, const T *__restrict__ block_partials, unsigned count,
+                                                              const uint32_t *__restrict__ active, size_t n, int map_op, T zero_u, T scale) {
+    __shared__ T wave_part[4];
+    addend_adjoint_finish<T>(out, block_partials, count, active, n, map_op, zero_u, scale, wave_part);
+}
+
+template <typename T> __global__ void k_scale_one(T *__restrict__ out, T scale) { out[0] = out[0] * scale; }
+
+/// out[0] = scale * (the sum of plane 0 over the entries + the dropped lanes' terms when `count_dropped`): the object holds early
+/// sums of map_op
+template <typename T>
+static int bucketed_addend_adjoint_fold(Bucketed *b, int map_op, T scale, void *out, bool count_dropped) {
+    Context &c = ctx();
+    const unsigned grid = fold_grid(b->table_size);
+    Scratch partials;
+    if (int rc = partials.alloc((size_t) grid * sizeof(T))) return rc;
+    const uint32_t *active = count_dropped ? b->masked_ptr() : nullptr;
+    const uint32_t *xmax = b->early_fixed ? b->active + (kPgMetaResultXmax - kPgMetaResult) : nullptr;
+    const size_t slot = b->early_fixed ? sizeof(long long) : sizeof(T);
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, c.stream, (T *) out, (T *) partials.ptr, b->ticket, (const void *) b->early,
+                           (const uint32_t *) b->early_modes, (const uint32_t *) b->piece_prefix, b->table_size, b->shift, xmax, b->early_S0,
+                           active, b->n, map_op, b->template dropped_u<T>(), scale);
+    };
+    if constexpr (std::is_same_v<T, float>) {
+        if (b->early_fixed) go(k_addend_adjoint_fold<float, true>); else go(k_addend_adjoint_fold<float, false>);
+    } else {
+        go(k_addend_adjoint_fold<T, false>);
+    }
+    EK_LAUNCH_CHECK("addend_adjoint_fold", b->table_size, (size_t) b->max_pieces * b->bins() * slot + (size_t) grid * sizeof(T));
+    if (!b->ticket) {
+        hipLaunchKernelGGL((k_addend_adjoint_final<T>), dim3(1), dim3(256), 0, c.stream, (T *) out, (const T *) partials.ptr, grid, active,
+                           b->n, map_op, b->template dropped_u<T>(), scale);
+        EK_LAUNCH_CHECK("reduce_stage2", (size_t) grid, (size_t) grid * sizeof(T) + sizeof(T));
+    }
+    return EK_OK;
+}
+
 template <typename T>
 static int bucketed_scatter_add(Bucketed *b, int count, void *const *bases, const int *from_u, const int *map_ops,
                                 const uint64_t *imm_bits, const int *weighted, const int *fresh, const uint64_t *scale_bits) {
@@ -1396,9 +1565,10 @@ using namespace ek;
 // goes to entries [s span, (s + 1) span) of its tables.
 struct ek_hip_bucketed : ek::Bucketed {
     std::vector<ek_hip_bucketed *> slices;
+    void *addend_table = nullptr;    // owned: the addend table of an object made from a DEVICE scalar (ek_hip_bucketed_pair_create_scalar_device)
     size_t slice_span = 0;
     bool slices_split = false;       // the slices hold disjoint parts of the input (CoarseSplit) instead of filtered views of all of it
-    ~ek_hip_bucketed() { for (ek_hip_bucketed *s : slices) delete s; }
+    ~ek_hip_bucketed() { for (ek_hip_bucketed *s : slices) delete s; if (addend_table) ek_hip_free(addend_table); }
 };
 struct SliceCounts { const uint32_t *active[kMaxSlices]; const uint32_t *flag; };
 
@@ -1412,6 +1582,19 @@ __global__ __launch_bounds__(64) void k_slices_combine(T *__restrict__ out, cons
     bool nonfinite = counts.flag && counts.flag[0];
     for (int s = 0; s < slices; ++s) { r = R::combine(r, partial[s]); kept += counts.active[s][0]; nonfinite = nonfinite || counts.active[s][1]; }
     out[0] = ek::bucket_dropped_lanes<T, ROp>(r, n - kept, nonfinite, map_op, zero_u);
+}
+
+/// ek_hip_bucketed_addend_adjoint over the slices of a large table: the slices' sums in slice order, the lanes NO slice kept counted
+/// once, the caller's factor -- one rounding behind the sum, as the last workgroup of k_addend_adjoint_fold applies it
+__global__ __launch_bounds__(64) void k_addend_adjoint_combine(float *__restrict__ out, const float *__restrict__ partial, int slices,
+                                                               SliceCounts counts, size_t n, int map_op, float zero_u, float scale) {
+    if (threadIdx.x != 0) return;
+    float r = 0.f;
+    size_t kept = 0;
+    bool nonfinite = counts.flag && counts.flag[0];
+    for (int s = 0; s < slices; ++s) { r += partial[s]; kept += counts.active[s][0]; nonfinite = nonfinite || counts.active[s][1]; }
+    const float all = ek::bucket_dropped_lanes<float, EK_HSUM>(r, n - kept, nonfinite, map_op, zero_u);
+    out[0] = scale != 1.f ? all * scale : all;
 }
 
 // (tables of three or more slices under a mask: the split by slice drops the masked-out lanes before any page partition sees
@@ -1576,6 +1759,30 @@ int ek_hip_bucketed_pair_create_scalar(int type, int index_type, int op, const v
     return bucketed_pair_create(type, index_type, op, table_a, nullptr, &addend_bits, table_size, x, index, mask, n, hints, out, EK_ERR_INVALID);
 }
 
+int ek_hip_bucketed_pair_create_scalar_device(int type, int index_type, int op, const void *table_a, const void *addend, size_t table_size,
+                                              const void *x, const void *index, const uint8_t *mask, size_t n, unsigned hints,
+                                              ek_hip_bucketed **out) {
+    if (int rc = ensure_init()) return rc;
+    if (!out || !table_a || !addend || !x || !index) return fail(EK_ERR_INVALID, "ek_hip_bucketed_pair_create_scalar_device(): null pointer");
+    *out = nullptr;
+    if (op != EK_FMADD && op != EK_FMSUB && op != EK_FNMADD && op != EK_FNMSUB && op != EK_MULADD && op != EK_MULSUB && op != EK_NMULADD)
+        return fail(EK_ERR_INVALID, "ek_hip_bucketed_pair_create_scalar_device(): op %d is neither of the fma family nor a product-then-sum", op);
+    if (mask) return fail(EK_ERR_UNSUPPORTED, "ek_hip_bucketed_pair_create_scalar_device(): a device scalar under a mask is not covered");
+    if (!ek_hip_bucketed_applicable(type, index_type, table_size, n))
+        return fail(EK_ERR_UNSUPPORTED, "ek_hip_bucketed_pair_create_scalar_device(): shape not covered (type %d, %zu lookups into %zu entries)",
+                    type, n, table_size);
+    // the scalar, broadcast on the stream into a table the object owns: from here on the object is the two-table one
+    void *table = nullptr;
+    const size_t elem = type == EK_F64 ? sizeof(double) : sizeof(float);
+    if (int rc = ek_hip_malloc(table_size * elem, &table)) return rc;
+    const ek_operand c{ addend, 0, 1 };
+    int rc = ek_hip_unary(EK_COPY, type, table, &c, table_size);
+    if (rc == EK_OK) rc = bucketed_pair_create(type, index_type, op, table_a, table, nullptr, table_size, x, index, nullptr, n, hints, out, EK_ERR_INVALID);
+    if (rc != EK_OK) { ek_hip_free(table); return rc; }
+    (*out)->addend_table = table;
+    return EK_OK;
+}
+
 int ek_hip_bucketed_reduce(ek_hip_bucketed *b, int reduce_op, int map_op, void *out, int keep_values, int keep_op) {
     if (int rc = ensure_init()) return rc;
     if (!b || !out) return fail(EK_ERR_INVALID, "ek_hip_bucketed_reduce(): null pointer");
@@ -1636,6 +1843,71 @@ int ek_hip_bucketed_scatter_add_scaled(ek_hip_bucketed *b, int count, void *cons
     }
     if (b->type == EK_F32) return bucketed_scatter_add<float>(b, count, bases, from_u, map_ops, imm_bits, weighted, fresh, scale_bits);
     return bucketed_scatter_add<double>(b, count, bases, from_u, map_ops, imm_bits, weighted, fresh, scale_bits);
+}
+
+int ek_hip_bucketed_addend_adjoint(ek_hip_bucketed *b, int map_op, uint64_t scale_bits, void *out) {
+    if (int rc = ensure_init()) return rc;
+    if (!b || !out) return fail(EK_ERR_INVALID, "ek_hip_bucketed_addend_adjoint(): null pointer");
+    if (!b->scalar_addend && !b->addend_table) return fail(EK_ERR_INVALID, "ek_hip_bucketed_addend_adjoint(): the object has no scalar addend");
+    if (map_op != EK_COPY && !unary_chainable(map_op))
+        return fail(EK_ERR_INVALID, "ek_hip_bucketed_addend_adjoint(): op %d cannot be applied on load", map_op);
+    Context &c = ctx();
+    const bool f64 = b->type == EK_F64;
+    float scale_f = 1.f;
+    double scale_d = 1.0;
+    if (f64) memcpy(&scale_d, &scale_bits, sizeof(double)); else memcpy(&scale_f, &scale_bits, sizeof(float));
+    // the forward pass left the sums of exactly this function per table entry (in every slice): one fold over plane 0
+    bool early = b->slices.empty() ? b->has_early && b->early_op == map_op : true;
+    for (const ek_hip_bucketed *sub : b->slices) early = early && sub->has_early && sub->early_op == map_op;
+    if (early && !b->slices.empty()) {
+        // a slice's sum leaves out the lanes the slice dropped (most of them are another slice's): they are counted ONCE, below
+        Scratch partial;
+        if (int rc = partial.alloc(b->slices.size() * sizeof(float))) return rc;
+        SliceCounts counts{};
+        int S = 0;
+        for (ek_hip_bucketed *sub : b->slices) {
+            if (int rc = bucketed_addend_adjoint_fold<float>(sub, map_op, 1.f, (float *) partial.ptr + S, false)) return rc;
+            counts.active[S++] = sub->active;
+        }
+        counts.flag = (const uint32_t *) b->meta;
+        hipLaunchKernelGGL(k_addend_adjoint_combine, dim3(1), dim3(64), 0, c.stream, (float *) out, (const float *) partial.ptr, S,
+                           counts, b->n, map_op, b->dropped_u<float>(), scale_f);
+        EK_LAUNCH_CHECK("reduce_stage2", (size_t) S, (size_t) S * sizeof(float));
+        return EK_OK;
+    } else if (early) {
+        return f64 ? bucketed_addend_adjoint_fold<double>(b, map_op, scale_d, out, true)
+                   : bucketed_addend_adjoint_fold<float>(b, map_op, scale_f, out, true);
+    } else {
+        // no such sums: the bucket-ordered reduction, one more pass over the pages (every lane counted, the dropped ones included)
+        if (int rc = ek_hip_bucketed_reduce(b, EK_HSUM, map_op, out, 0, EK_COPY)) return rc;
+    }
+    // (the reduction wrote the plain sum: the factor is one more one-thread launch on this path only)
+    if (f64 ? scale_d != 1.0 : scale_f != 1.f) {
+        if (f64) hipLaunchKernelGGL((k_scale_one<double>), dim3(1), dim3(1), 0, c.stream, (double *) out, scale_d);
+        else hipLaunchKernelGGL((k_scale_one<float>), dim3(1), dim3(1), 0, c.stream, (float *) out, scale_f);
+        EK_LAUNCH_CHECK("addend_adjoint_scale", (size_t) 1, 2 * (f64 ? sizeof(double) : sizeof(float)));
+    }
+    return EK_OK;
+}
+
+int ek_hip_bucketed_piece_counts(ek_hip_bucketed *b, uint32_t *pieces, uint32_t *largest) {
+    if (int rc = ensure_init()) return rc;
+    if (!b || !pieces || !largest) return fail(EK_ERR_INVALID, "ek_hip_bucketed_piece_counts(): null pointer");
+    if (int busy = refuse_while_capturing("ek_hip_bucketed_piece_counts()")) return busy;
+    *pieces = *largest = 0;
+    std::vector<const ek_hip_bucketed *> objs;
+    if (b->slices.empty()) objs.push_back(b);
+    for (const ek_hip_bucketed *sub : b->slices) objs.push_back(sub);
+    std::vector<uint32_t> prefix;
+    for (const ek_hip_bucketed *o : objs) {
+        if (!o->piece_prefix || o->n_buckets <= 0) continue;
+        prefix.assign((size_t) o->n_buckets + 1, 0u);
+        EK_HIP_CHECK(hipMemcpyAsync(prefix.data(), o->piece_prefix, prefix.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx().stream));
+        EK_HIP_CHECK(hipStreamSynchronize(ctx().stream));
+        *pieces += prefix[(size_t) o->n_buckets] - prefix[0];
+        for (int k = 0; k < o->n_buckets; ++k) *largest = std::max(*largest, prefix[(size_t) k + 1] - prefix[(size_t) k]);
+    }
+    return EK_OK;
 }
 
 int ek_hip_bucketed_destroy(ek_hip_bucketed *b) {

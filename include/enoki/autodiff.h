@@ -253,7 +253,8 @@ template <typename Type_> struct DiffArray : ArrayTag {
     //  Differentiable vertical operations.  Edge weights follow autodiff.h:219-757.
     // -----------------------------------------------------------------------------------------
     /// A host scalar that requires a gradient, next to a backend that would leave `gather * x + scalar` unevaluated for its
-    /// bucket-ordered path: that path does not cover a differentiable addend, the expression keeps its element-order kernels
+    /// bucket-ordered path: the backend's guard decides whether that path covers a differentiable addend (HIPArray: when the
+    /// library can sum the addend's gradient on the partition -- hsum_safe_mul_) or the expression keeps its element-order kernels
     static bool diff_scalar_(const DiffArray &a) {
         if constexpr (Enabled && detail::has_scalar_addend_guard<Type>::value) return a.m_index != 0 && a.m_value.is_immediate();
         else return false;

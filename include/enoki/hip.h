@@ -103,8 +103,12 @@ namespace detail {
             uint64_t imm[3] = { 0, 0, 0 };
             bool is_imm[3] = { false, false, false };
             HIPBuffer *operand_buf(int k) const { return k == 0 ? table : k == 1 ? arg0 : table2; }
-            bool scalar_addend() const { return kind == 2 && !table2 && is_imm[2]; }
-            bool product_alone() const { return kind == 2 && !table2 && !is_imm[2]; }
+            // ... or with a size-1 DEVICE array as that scalar (`addend`, a held reference; the node is among its readers, so a write
+            // to c evaluates the node first): the state of a trained bias after `c = c - lr * gradient(c)`.  The value is never
+            // read by the host (ek_hip_bucketed_pair_create_scalar_device reads it on the stream).
+            HIPBuffer *addend = nullptr;
+            bool scalar_addend() const { return kind == 2 && !table2 && (is_imm[2] || addend); }
+            bool product_alone() const { return kind == 2 && !table2 && !is_imm[2] && !addend; }
         };
         Deferred *deferred = nullptr;
         std::vector<HIPBuffer *> readers;      // deferred nodes whose table / source is THIS buffer (not owning)
@@ -297,10 +301,14 @@ namespace detail {
             if (!d->bucketed && d->scalar_addend()) {
                 // (EK_OPTIONAL in enoki_hip.h: a C ABI that predates the entry, or a host stand-in of it, leaves the address null --
                 //  "shape not covered", the expression runs in element order with the same bits)
-                if (!&ek_hip_bucketed_pair_create_scalar) return nullptr;
-                int rc = ek_hip_bucketed_pair_create_scalar(d->type, d->index_type, d->op, d->table->ptr, d->imm[2], d->table->size, d->arg0->ptr,
-                                                            d->index->ptr, d->mask ? (const uint8_t *) d->mask->ptr : nullptr, size, hints,
-                                                            &d->bucketed);
+                if (d->addend ? !&ek_hip_bucketed_pair_create_scalar_device : !&ek_hip_bucketed_pair_create_scalar) return nullptr;
+                int rc = d->addend
+                    ? ek_hip_bucketed_pair_create_scalar_device(d->type, d->index_type, d->op, d->table->ptr, d->addend->ptr, d->table->size,
+                                                                d->arg0->ptr, d->index->ptr, d->mask ? (const uint8_t *) d->mask->ptr : nullptr,
+                                                                size, hints, &d->bucketed)
+                    : ek_hip_bucketed_pair_create_scalar(d->type, d->index_type, d->op, d->table->ptr, d->imm[2], d->table->size, d->arg0->ptr,
+                                                         d->index->ptr, d->mask ? (const uint8_t *) d->mask->ptr : nullptr, size, hints,
+                                                         &d->bucketed);
                 if (rc == EK_ERR_UNSUPPORTED) return nullptr;
                 hip_check(rc, "HIPArray (bucket partition)");
             } else if (!d->bucketed) {
@@ -358,7 +366,7 @@ namespace detail {
             void *p = nullptr;
             hip_check(ek_hip_malloc((size ? size : 1) * d->elem_size, &p), "HIPArray (deferred fma of a gather and a scalar)");
             ek_gathered g = gathered();
-            ek_operand x{ d->arg0->ptr, 0, d->arg0->size }, c{ nullptr, d->imm[2], 1 };
+            ek_operand x{ d->arg0->ptr, 0, d->arg0->size }, c{ d->addend ? d->addend->ptr : nullptr, d->addend ? 0 : d->imm[2], 1 };
             const ek_gathered *pg[3] = { &g, nullptr, nullptr };
             const ek_operand *po[3] = { nullptr, &x, &c };
             int rc;
@@ -479,7 +487,7 @@ namespace detail {
             pending_unlink();
             if (d->partner && d->partner->deferred) d->partner->deferred->partner = nullptr;
             if (d->bucketed) ek_hip_bucketed_destroy(d->bucketed);
-            for (HIPBuffer *src : { d->table, d->index, d->mask, d->table2, d->arg0 }) {
+            for (HIPBuffer *src : { d->table, d->index, d->mask, d->table2, d->arg0, d->addend }) {
                 if (!src) continue;
                 auto &r = src->readers;
                 for (size_t i = 0; i < r.size(); ++i)
@@ -490,6 +498,7 @@ namespace detail {
             unref(d->mask);
             unref(d->table2);
             unref(d->arg0);
+            unref(d->addend);
             delete d;
         }
 
@@ -838,6 +847,7 @@ template <typename Value_> struct HIPArray : ArrayTag {
     /// hsum(safe_mul(w, g)) in one pass
     static HIPArray hsum_safe_mul_(const HIPArray &w, const HIPArray &g) {
         w.require_valid("hsum_safe_mul"); g.require_valid("hsum_safe_mul");
+        if (HIPArray r = addend_adjoint_(w, g); r.valid()) return r;
         size_t n = broadcast_size(w.size(), g.size());
         HIPArray r = empty_(1);
         ek_operand ow = w.operand(), og = g.operand();
@@ -1086,16 +1096,20 @@ template <typename Value_> struct HIPArray : ArrayTag {
     static void note_plain_addend_(const char *shape, const HIPArray &c, size_t n) {
         const char *why = !c.m_buf ? "the addend is not initialized"
             : c.m_buf->deferred ? "the addend is itself unevaluated (a unary map, an arithmetic node, or a gather that does not share index array, mask and table size with the product's)"
-            : c.m_buf->size == 1 ? "the addend is a size-1 DEVICE array, not a host scalar (its value is not known on the host)"
+            : c.m_buf->size == 1 ? (c.m_buf->view_of || !c.m_buf->owned ? "the size-1 device addend is a view / foreign memory"
+                                    : c.m_buf->exported ? "the size-1 device addend has a zero-copy export (an external writer could change it)"
+                                    : "the size-1 device addend is of another type, or the library has no ek_hip_bucketed_pair_create_scalar_device")
             : c.m_buf->size == n ? "the addend is an n-element array (only a gather through the same index array or a host scalar stays in bucket order)"
             : "the addend has another length";
         detail::hip_note_element_order(shape, why);
     }
 
-    /// While an armed one is alive, a host-scalar addend next to a gathered product does not make a kind-2 node.  DiffArray holds one
-    /// around an addend that REQUIRES A GRADIENT: that shape is outside the bucket-ordered path and keeps its element-order kernels.
+    /// While an armed one is alive, a host-scalar addend next to a gathered product does not make a kind-2 node.  DiffArray asks for one
+    /// around an addend that REQUIRES A GRADIENT.  It arms only against a C ABI without ek_hip_bucketed_addend_adjoint (EK_OPTIONAL: the
+    /// address is null): with the entry the addend's gradient is a fold of the early sums (hsum_safe_mul_), without it that shape keeps
+    /// its element-order kernels.
     struct ScalarAddendGuard {
-        explicit ScalarAddendGuard(bool armed) : armed(armed) { if (armed) ++detail::HIPBuffer::shared().scalar_addend_off; }
+        explicit ScalarAddendGuard(bool wanted) : armed(wanted && !&ek_hip_bucketed_addend_adjoint) { if (armed) ++detail::HIPBuffer::shared().scalar_addend_off; }
         ~ScalarAddendGuard() { if (armed) --detail::HIPBuffer::shared().scalar_addend_off; }
         ScalarAddendGuard(const ScalarAddendGuard &) = delete;
         ScalarAddendGuard &operator=(const ScalarAddendGuard &) = delete;
@@ -1112,8 +1126,15 @@ template <typename Value_> struct HIPArray : ArrayTag {
             const char *shape = "fma(gather(A, idx), x, c) with a host scalar c";
             const auto *p = g.m_buf->deferred;
             detail::HIPBuffer *xb = p->kind == 2 ? p->arg0 : x.m_buf;
-            if (!detail::hip_defer_gather_flag() || !c.m_is_imm || g.m_buf->size != n) return r;
-            if (detail::HIPBuffer::shared().scalar_addend_off) { detail::hip_note_element_order(shape, "the scalar addend requires a gradient"); return r; }
+            // c: a host scalar, or an evaluated, owned, non-exported size-1 array of the element type (its value stays on the device)
+            detail::HIPBuffer *cb = c.m_is_imm ? nullptr : c.m_buf;
+            if (!detail::hip_defer_gather_flag() || g.m_buf->size != n) return r;
+            if (cb) {
+                if (cb->deferred || cb->size != 1 || !cb->ptr) { note_plain_addend_(shape, c, n); return r; }
+                if (!cb->owned || cb->exported || cb->view_of || !&ek_hip_bucketed_pair_create_scalar_device) { note_plain_addend_(shape, c, n); return r; }
+                if (p->mask) { detail::hip_note_element_order(shape, "a size-1 device addend under a MASKED gather (a dropped lane's u is the scalar, which only the host-scalar kernels carry)"); return r; }
+            }
+            if (!cb && detail::HIPBuffer::shared().scalar_addend_off) { detail::hip_note_element_order(shape, "the scalar addend requires a gradient"); return r; }
             if (p->kind != 2) {
                 if (x.m_is_imm || !xb || xb->size != n) { detail::hip_note_element_order(shape, "x is a scalar / of another length"); return r; }
                 if (!xb->owned || xb->exported) { detail::hip_note_element_order(shape, "x is a view of foreign memory or has a zero-copy export (an external writer could change it)"); return r; }
@@ -1129,15 +1150,15 @@ template <typename Value_> struct HIPArray : ArrayTag {
                                                                 false, 2, nullptr };
             d->arg0 = xb;
             d->op = op;
-            d->is_imm[2] = true;
-            d->imm[2] = imm_bits(c.m_imm);
+            if (cb) d->addend = cb;
+            else { d->is_imm[2] = true; d->imm[2] = imm_bits(c.m_imm); }
             r.m_buf = new detail::HIPBuffer();
             r.m_buf->size = n;
             r.m_buf->deferred = d;
             r.m_buf->pending_link();
-            detail::HIPBuffer *seen[4] = { nullptr, nullptr, nullptr, nullptr };
+            detail::HIPBuffer *seen[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
             int k = 0;
-            for (detail::HIPBuffer *src : { d->table, d->index, d->arg0, d->mask }) {
+            for (detail::HIPBuffer *src : { d->table, d->index, d->arg0, d->mask, d->addend }) {
                 if (!src) continue;
                 src->ref_count++;
                 bool dup = false;
@@ -1388,6 +1409,41 @@ template <typename Value_> struct HIPArray : ArrayTag {
             }
             ga.m_buf->deferred->consumed = true;
             gc.m_buf->deferred->consumed = true;
+        }
+        return r;
+    }
+
+    /// hsum(safe_mul(w, g)) with w a host scalar and g an unevaluated (optionally scaled) unary map f'(u) of a kind-2 node with a
+    /// scalar addend -- what Tape::backward() asks for as the gradient of that addend (a size-1 source under a vector target): the
+    /// sum over u's lanes, answered on u's partition (ek_hip_bucketed_addend_adjoint: a fold of the sums the forward pass formed per
+    /// table entry, or one bucket-ordered reduction).  w * scale is the factor on the sum.  Invalid array: not that shape, or not
+    /// covered -- the caller evaluates g, and with it u, in element order.
+    static HIPArray addend_adjoint_(const HIPArray &w, const HIPArray &g) {
+        HIPArray r;
+        if constexpr (IsFloat) {
+            if (!w.m_is_imm || !g.mapped_() || !&ek_hip_bucketed_addend_adjoint) return r;
+            const auto *m = g.m_buf->deferred;
+            detail::HIPBuffer *u = m->table;
+            if (!u->deferred || !u->deferred->scalar_addend() || u->size <= 1) return r;
+            const char *shape = "gradient of the scalar addend c of fma(gather(A, idx), x, c)";
+            if (!map_on_load_(m->index_type)) { detail::hip_note_element_order(shape, "the derivative is not a function the bucket-ordered kernels apply on load"); return r; }
+            const Value factor = w.m_imm * g.map_scale_();
+            // (safe_mul: a zero weight gives zero whatever g holds; a factor that is not finite keeps the lane-by-lane products)
+            if (w.m_imm == Value(0)) {
+                // (a size-1 DEVICE array like every other answer of hsum_safe_mul_, not an immediate)
+                r = empty_(1);
+                detail::hip_check(ek_hip_memset(r.m_buf->ptr, 0, sizeof(Value)), "hsum_safe_mul");
+                return r;
+            }
+            if (!(factor == factor) || factor - factor != Value(0)) { detail::hip_note_element_order(shape, "the weight is not finite"); return r; }
+            ek_hip_bucketed *b = u->bucketed();
+            if (!b) { detail::hip_note_element_order(shape, "the library does not cover the shape (deterministic mode, ENOKI_HIP_BUCKET_ORDERED=0)"); return r; }
+            r = empty_(1);
+            int rc = ek_hip_bucketed_addend_adjoint(b, m->index_type, imm_bits(factor), r.m_buf->ptr);
+            if (rc == EK_ERR_UNSUPPORTED) { detail::hip_note_element_order(shape, "the library does not cover the function"); return HIPArray(); }
+            detail::hip_check(rc, "HIPArray (gradient of a scalar addend, bucket order)");
+            if (ek_hip_log_level() >= 2)
+                fprintf(stderr, "enoki-hip: [bucket order] %s: summed on u's partition (the early sums per table entry, or one bucket-ordered reduction)\n", shape);
         }
         return r;
     }
@@ -1749,9 +1805,10 @@ template <typename Value_> struct HIPArray : ArrayTag {
             case 1: return std::string("unevaluated unary op ") + std::to_string(d->index_type) + (d->scaled ? " times a host scalar" : "") + ", " + n +
                            ": reductions and scatter_add value streams apply it while loading; source " +
                            (d->table->deferred ? "unevaluated (kind " + std::to_string(d->table->deferred->kind) + ")" : "evaluated");
-            case 2: return "unevaluated " + std::string(d->scalar_addend() ? (d->op >= EK_MULADD ? "product of a gather with an array, then sum with a host scalar" : "fma of a gather, an array and a host scalar") : !d->table2 ? "product of a gather with an array" : d->op >= EK_MULADD ? "product-then-sum of two gathers through one index array" : "fma of two gathers through one index array") + " (K = " +
+            case 2: return "unevaluated " + std::string(d->scalar_addend() ? (d->op >= EK_MULADD ? (d->addend ? "product of a gather with an array, then sum with a size-1 device addend" : "product of a gather with an array, then sum with a host scalar") : (d->addend ? "fma of a gather, an array and a size-1 device addend" : "fma of a gather, an array and a host scalar")) : !d->table2 ? "product of a gather with an array" : d->op >= EK_MULADD ? "product-then-sum of two gathers through one index array" : "fma of two gathers through one index array") + " (K = " +
                            std::to_string(d->table->size) + ", " + n + "): BUCKET ORDER possible -- a horizontal reduction (directly or through one fusable "
                            "unary op) and the adjoint scatter_add of the gathers stay in bucket order; any other access evaluates it in element order" +
+                           (d->scalar_addend() && &ek_hip_bucketed_addend_adjoint ? "; the gradient of the scalar, if it requires one, is summed on the partition" : "") +
                            (d->bucketed ? "; partition built" : "");
             case 3: return "zeros that nobody has looked at, " + n;
             case 4: return "unevaluated arithmetic op " + std::to_string(d->op) + " of arity " + std::to_string(d->arity) + " over evaluated operands, " + n +
@@ -1988,7 +2045,7 @@ private:
                 // a gathered factor next to a HOST-SCALAR addend (`fmadd(gather(A, idx), x, 0.5f)`): stays unevaluated for bucket order
                 const HIPArray &c = *x[2];
                 const char *shape = "fma(gather(A, idx), x, c)";
-                if (c.m_is_imm) {
+                if (c.m_is_imm || (c.m_buf && c.m_buf->size == 1 && !c.m_buf->deferred)) {
                     if (HIPArray r = defer_scalar_addend_(op, *x[d[0] ? 0 : 1], *x[d[0] ? 1 : 0], c, n); r.valid()) {
                         result = std::move(r);
                         return true;
@@ -2086,7 +2143,7 @@ private:
             if ((op == EK_ADD || op == EK_SUB) && (gathered_product_() || b.gathered_product_())) {
                 const HIPArray &pr = gathered_product_() ? *this : b, &c = gathered_product_() ? b : *this;
                 const char *shape = "gather(A, idx) * x +- c";
-                if (c.m_is_imm && pr.m_buf->size == n) {
+                if ((c.m_is_imm || (c.m_buf && c.m_buf->size == 1 && !c.m_buf->deferred)) && pr.m_buf->size == n) {
                     const int form = op == EK_ADD ? EK_MULADD : (&pr == this ? EK_MULSUB : EK_NMULADD);
                     if (HIPArray r = defer_scalar_addend_(form, pr, pr, c, n); r.valid()) return r;
                 } else if (!c.m_is_imm) {

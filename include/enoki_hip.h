@@ -336,6 +336,36 @@ EK_API int ek_hip_bucketed_pair_create_masked(int type, int index_type, int op, 
 EK_API EK_OPTIONAL int ek_hip_bucketed_pair_create_scalar(int type, int index_type, int op, const void *table_a, uint64_t addend_bits,
                                               size_t table_size, const void *x, const void *index, const uint8_t *mask, size_t n,
                                               unsigned hints, ek_hip_bucketed **out);
+/* create_scalar_device: create_scalar with the scalar in DEVICE memory -- `addend` points to one element of the object's type, the
+ * state of a trained bias after `c = c - lr * gradient(c)` (the tape's size-1 gradient, autodiff.cpp:851-853, makes c a size-1
+ * array).  The element is read ON THE STREAM, never by the host: no synchronisation, no read-back, so the object can be created and
+ * used inside ek_hip_graph_begin / _end and a replay sees the value *addend holds at replay time.  The call broadcasts the element
+ * into a table of table_size entries that the object owns (one launch, 4 or 8 B per entry) and every later call on the object reads
+ * the scalar from there with the kernels of the two-table object -- the kernels of the benchmark's step, unchanged; a NaN or
+ * infinite value sends the fixed-point pieces down the lock path at run time like a non-finite table entry.  The caller keeps
+ * `addend` alive and unchanged for the lifetime of the object, like the tables.  ek_hip_bucketed_addend_adjoint accepts the
+ * object.  mask must be NULL (EK_ERR_UNSUPPORTED otherwise: a lane the partition drops would have to count map_op(+-c), which
+ * only the host-scalar kernels carry; a lane whose index points outside the table counts map_op(0) here, as for two tables).
+ * Ops, hints, shapes and the other return codes as for create_scalar.  EK_OPTIONAL like create_scalar. */
+EK_API EK_OPTIONAL int ek_hip_bucketed_pair_create_scalar_device(int type, int index_type, int op, const void *table_a, const void *addend,
+                                              size_t table_size, const void *x, const void *index, const uint8_t *mask, size_t n,
+                                              unsigned hints, ek_hip_bucketed **out);
+/* addend_adjoint: out[0] = scale * (sum over ALL n lanes of map_op(u_i)), one element of the object's type on the device -- the
+ * gradient of the scalar addend c of  y = hsum(f(u)),  u = op(A[index], x, c),  with map_op = f': the tape's edge from u to a
+ * size-1 source sums weight * gradient over u's entries (autodiff.cpp:851-853 broadcasts the size-1 gradient first, :1191-1199
+ * forms the edge product).  The sign of du/dc (-1 for EK_FMSUB / EK_FNMSUB / EK_MULSUB) is the tape's edge weight and is NOT
+ * applied here; scale_bits: a host factor, bits of the element type.
+ * When the object holds early sums of exactly map_op (reduce(EK_HSUM, f, keep, map_op) of a hinted object ran), plane 0 of the
+ * per-piece tables is folded by ONE launch: per table entry the value scatter_add would fold into a fresh table for the unweighted
+ * stream (fixed-point pieces added as 128-bit integers, converted once and scaled back; float pieces on top), the entry values
+ * added in an order fixed by the entry index alone (deterministic; with fixed-point sums bit-identical from run to run).  Without
+ * such sums: ek_hip_bucketed_reduce(b, EK_HSUM, map_op, ..) -- one more pass over the lists, never element order.  The lanes the
+ * partition dropped have u = +-c and count map_op(+-c) each, ONCE for a sliced table; NaN when one of them carried a non-finite x
+ * (as the forward value).  scale is applied to the finished sum inside the fold's last step (a sliced table: inside the launch that
+ * combines the slices); only the reduction path needs one more one-thread launch for a scale other than 1.
+ * An object without a scalar addend, or a map_op ek_hip_reduce_map refuses: EK_ERR_INVALID.
+ * EK_OPTIONAL: without the entry enoki/hip.h keeps a scalar addend that requires a gradient in element order. */
+EK_API EK_OPTIONAL int ek_hip_bucketed_addend_adjoint(ek_hip_bucketed *b, int map_op, uint64_t scale_bits, void *out);
 EK_API int ek_hip_bucketed_reduce(ek_hip_bucketed *b, int reduce_op, int map_op, void *out, int keep_values, int keep_op);
 EK_API int ek_hip_bucketed_scatter_add(ek_hip_bucketed *b, int count, void *const *bases, const int *from_u, const int *map_ops,
                                        const uint64_t *imm_bits, const int *weighted, const int *fresh);
@@ -348,6 +378,11 @@ EK_API int ek_hip_bucketed_scatter_add_scaled(ek_hip_bucketed *b, int count, voi
 /* != 0: a hinted object sums keep_op(u) and x * keep_op(u) per table entry inside reduce(EK_HSUM, map_op, keep, keep_op):
  * {sin, cos}, {cos, sin}, {log, rcp} and {f, f} for f in neg abs sqrt rcp rsqrt sin cos exp log */
 EK_API int ek_hip_bucketed_early_pair(int map_op, int keep_op);
+/* diagnostics: how the partition cut the object's buckets -- *pieces: pieces that exist (all slices of a large table together),
+ * *largest: the most pieces any ONE bucket was cut into (1: every populated bucket is one piece; the per-piece tables of the early
+ * sums then hold floats, see ek_hip_bucketed_scatter_add).  Reads the piece prefix back: synchronises, refuses while a step graph
+ * is being captured. */
+EK_API int ek_hip_bucketed_piece_counts(ek_hip_bucketed *b, uint32_t *pieces, uint32_t *largest);
 EK_API int ek_hip_bucketed_destroy(ek_hip_bucketed *b);
 /* ---- multi-GPU without python / torch (csrc/dist.cpp) -------------------------------------------------------------------------
  * One process per GPU.  Index-range sharding: rank r owns [r n / P, (r + 1) n / P) of EVERY size-n array (ek_hip_dist_shard_range),
