@@ -45,8 +45,9 @@ namespace detail {
     /// The reference never writes a gather that feeds an arithmetic op to memory -- its JIT fuses the load into the
     /// consumer (jit.cu:1066-1217) -- and neither does HIPArray: the first add/sub/mul/fma that consumes a deferred gather
     /// reads the table in place (ek_hip_map_gathered); any other access (data(), operand(), a second consumer, ...) runs
-    /// the plain gather kernel first.  Arrays stay immutable values: the deferred node holds references on its table,
-    /// index and mask buffers, and a buffer with deferred readers forces them before it hands out a mutable pointer.
+    /// the plain gather kernel first.  Arrays stay immutable values: an unevaluated node holds one reference per source slot
+    /// (Deferred::each_source()) and stands once in the `readers` of every distinct buffer among them -- make_pending() takes
+    /// both, drop_deferred() returns both -- and a buffer with readers forces them before it hands out a mutable pointer.
     struct HIPBuffer {
         void *ptr = nullptr;
         size_t size = 0;          // elements
@@ -61,10 +62,10 @@ namespace detail {
         /// evaluated inside the adjoint scatter_add of the gathers that produced u.  Any other access runs the plain
         /// kernel -- for the two halves of a sincos() ONE kernel that fills both, as before.
         struct Deferred {
-            HIPBuffer *table, *index, *mask;   // references held; mask == nullptr: every lane is active.  Map: table = source
-            int type, index_type;              // map: index_type holds the unary op
-            size_t elem_size;
-            bool consumed;                     // a fused consumer has read it once: the next access materialises (gathers)
+            HIPBuffer *table = nullptr, *index = nullptr, *mask = nullptr;   // references held; mask == nullptr: every lane is active.  Map: table = source
+            int type = 0, index_type = 0;      // map: index_type holds the unary op (map_op())
+            size_t elem_size = 0;
+            bool consumed = false;             // a fused consumer has read it once: the next access materialises (gathers)
             int kind = 0;                      // 0: gather, 1: unary map, 2: fma of a gathered pair (below), 3: zeros (no sources),
                                                // 4: arithmetic over evaluated operands (below)
             HIPBuffer *partner = nullptr;      // map: the other half of an unevaluated sincos pair (not owning)
@@ -109,6 +110,12 @@ namespace detail {
             HIPBuffer *addend = nullptr;
             bool scalar_addend() const { return kind == 2 && !table2 && (is_imm[2] || addend); }
             bool product_alone() const { return kind == 2 && !table2 && !is_imm[2] && !addend; }
+            int map_op() const { return index_type; }
+            /// Every buffer the node holds a reference on, slot by slot (one buffer may fill several): the ONE list of the source slots
+            template <typename F> void each_source(F &&f) const {
+                for (HIPBuffer *src : { table, index, mask, table2, arg0, addend })
+                    if (src) f(src);
+            }
         };
         Deferred *deferred = nullptr;
         std::vector<HIPBuffer *> readers;      // deferred nodes whose table / source is THIS buffer (not owning)
@@ -153,6 +160,31 @@ namespace detail {
         static void force_all_pending() {
             while (pending_head()) pending_head()->force();
         }
+        /// The unevaluated buffer of `n` elements for a filled node: linked into the pending list, one reference taken per source
+        /// slot, and registered once with every distinct source (a fresh buffer can only be the LAST reader of a source it has
+        /// already met) -- every buffer the node will read hands out mutable pointers only after the node has run
+        static HIPBuffer *make_pending(Deferred *d, size_t n) {
+            HIPBuffer *b = new HIPBuffer();
+            b->size = n;
+            b->deferred = d;
+            b->pending_link();
+            d->each_source([b](HIPBuffer *src) {
+                src->ref_count++;
+                if (src->readers.empty() || src->readers.back() != b) src->readers.push_back(b);
+            });
+            return b;
+        }
+        /// Evaluate the node into fresh storage: `launch(out)` fills it and returns an EK_* code; the node is gone afterwards
+        template <typename Launch> void evaluate(const char *what, Launch &&launch) {
+            void *p = nullptr;
+            hip_check(ek_hip_malloc((size ? size : 1) * deferred->elem_size, &p), what);
+            if (launch(p) != EK_OK) {
+                ek_hip_free(p);
+                hip_raise(what);
+            }
+            ptr = p;
+            drop_deferred();
+        }
         HIPBuffer *view_of = nullptr;          // a window into another buffer (HIPArray::view_): holds a reference on it
         // A 64-bit integer array that was narrowed to 32 bits keeps the result for as long as its contents cannot change (owning):
         // the gather, the tape's offset array (autodiff.h `Offset(index)`) and the adjoint scatter_add of ONE 64-bit index array then
@@ -191,17 +223,11 @@ namespace detail {
                 ek_chain ch;
                 build_chain(ch);
                 if (ch.n_maps > 1 || ch.arity > 1) {
-                    void *p = nullptr;
-                    hip_check(ek_hip_malloc(bytes, &p), "HIPArray (deferred chain)");
                     ek_operand factor{ nullptr, d->scale_bits, 1 };           // (a scaled node: one more rounding, inside the pass)
-                    int rc = d->scaled ? ek_hip_map_chain_product(d->type, p, nullptr, &ch, &factor, EK_MUL, nullptr, size)
-                                       : ek_hip_map_chain(d->type, p, &ch, size);
-                    if (rc != EK_OK) {
-                        ek_hip_free(p);
-                        hip_raise("HIPArray (deferred chain)");
-                    }
-                    ptr = p;
-                    drop_deferred();
+                    evaluate("HIPArray (deferred chain)", [&](void *p) {
+                        return d->scaled ? ek_hip_map_chain_product(d->type, p, nullptr, &ch, &factor, EK_MUL, nullptr, size)
+                                         : ek_hip_map_chain(d->type, p, &ch, size);
+                    });
                     return;
                 }
             }
@@ -214,11 +240,11 @@ namespace detail {
             if (other) {
                 rc = ek_hip_malloc(bytes, &q);
                 if (rc == EK_OK) {
-                    const bool is_sin = d->index_type == EK_SIN;
+                    const bool is_sin = d->map_op() == EK_SIN;
                     rc = ek_hip_sincos(d->type, is_sin ? p : q, is_sin ? q : p, &src, size);
                 }
             } else {
-                rc = ek_hip_unary(d->index_type, d->type, p, &src, size);
+                rc = ek_hip_unary(d->map_op(), d->type, p, &src, size);
             }
             if (rc != EK_OK) {
                 ek_hip_free(p);
@@ -253,46 +279,42 @@ namespace detail {
             Deferred *d = deferred;
             ek_chain ch;
             build_chain(ch);
-            void *p = nullptr;
-            hip_check(ek_hip_malloc((size ? size : 1) * d->elem_size, &p), "HIPArray (deferred map and its product)");
             ek_operand factor{ nullptr, d->scale_bits, 1 }, other{ w->ptr, 0, w->size };
-            if (ek_hip_map_chain_product(d->type, p, product, &ch, d->scaled ? &factor : nullptr, op2, &other, size) != EK_OK) {
-                ek_hip_free(p);
-                hip_raise("HIPArray (deferred map and its product)");
-            }
-            ptr = p;
-            drop_deferred();
+            evaluate("HIPArray (deferred map and its product)", [&](void *p) {
+                return ek_hip_map_chain_product(d->type, p, product, &ch, d->scaled ? &factor : nullptr, op2, &other, size);
+            });
         }
 
-        /// Element-order evaluation of a deferred fma over a gathered pair: one kernel, gathers consumed in place
+        /// Element-order evaluation of a kind-2 node, the gathers consumed in place -- the kernels and the bits of the eager
+        /// expression.  Two tables, or the fma family with a scalar addend: one kernel.  The product alone: the product that consumes
+        /// the gather.  The operator forms with a scalar addend: that product, and the sum with the scalar behind it, in place.
         void force_pair() {
             Deferred *d = deferred;
             hip_note_element_order("fma of two gathers through one index array",
                                    "evaluated in ELEMENT order -- its consumer is not a horizontal reduction (directly or through one "
                                    "fusable unary op) nor the adjoint scatter_add of its gathers, or a source is about to be written, or a "
                                    "step graph is being captured, or deterministic mode is on");
-            if (d->scalar_addend()) { force_scalar_addend(); return; }
-            if (!d->table2) { force_gathered_product(); return; }
-            void *p = nullptr;
-            hip_check(ek_hip_malloc((size ? size : 1) * d->elem_size, &p), "HIPArray (deferred fma of gathers)");
-            ek_gathered ga, gc;
-            ga.table = d->table->ptr;
-            ga.table_size = d->table->size;
-            ga.index = ek_operand{ d->index->ptr, 0, d->index->size };
-            ga.index_type = d->index_type;
-            ga.mask = d->mask ? ek_operand{ d->mask->ptr, 0, d->mask->size } : ek_operand{ nullptr, 1, 1 };
-            gc = ga;
-            gc.table = d->table2->ptr;
-            gc.table_size = d->table2->size;
-            ek_operand x{ d->arg0->ptr, 0, d->arg0->size };
-            const ek_gathered *pg[3] = { &ga, nullptr, &gc };
-            const ek_operand *po[3] = { nullptr, &x, nullptr };
-            if (ek_hip_map_gathered(3, d->op, d->type, p, po, pg, size) != EK_OK) {
-                ek_hip_free(p);
-                hip_raise("HIPArray (deferred fma of gathers)");
+            const bool scalar = d->scalar_addend();
+            ek_gathered ga = gathered(), gc = ga;
+            if (d->table2) {
+                gc.table = d->table2->ptr;
+                gc.table_size = d->table2->size;
             }
-            ptr = p;
-            drop_deferred();
+            ek_operand x{ d->arg0->ptr, 0, d->arg0->size }, c{ d->addend ? d->addend->ptr : nullptr, d->addend ? 0 : d->imm[2], 1 };
+            const ek_gathered *pg[3] = { &ga, nullptr, d->table2 ? &gc : nullptr };
+            const ek_operand *po[3] = { nullptr, &x, scalar ? &c : nullptr };
+            const char *what = d->table2 ? "HIPArray (deferred fma of gathers)"
+                             : scalar    ? "HIPArray (deferred fma of a gather and a scalar)" : "HIPArray (deferred product of a gather)";
+            evaluate(what, [&](void *p) {
+                if (!d->table2 && !scalar) return ek_hip_map_gathered(2, EK_MUL, d->type, p, po, pg, size);
+                if (d->table2 || !(d->op == EK_MULADD || d->op == EK_MULSUB || d->op == EK_NMULADD))
+                    return ek_hip_map_gathered(3, d->op, d->type, p, po, pg, size);
+                int rc = ek_hip_map_gathered(2, EK_MUL, d->type, p, po, pg, size);
+                ek_operand prod{ p, 0, size };
+                if (rc != EK_OK) return rc;
+                return d->op == EK_NMULADD ? ek_hip_binary(EK_SUB, d->type, p, &c, &prod, size)
+                                           : ek_hip_binary(d->op == EK_MULADD ? EK_ADD : EK_SUB, d->type, p, &prod, &c, size);
+            });
         }
 
         /// The bucket partition of a kind-2 node (built on first use); nullptr when the library does not cover the shape
@@ -324,67 +346,15 @@ namespace detail {
         /// kind 4: run the deferred arithmetic op
         void force_arith() {
             Deferred *d = deferred;
-            void *p = nullptr;
-            hip_check(ek_hip_malloc((size ? size : 1) * d->elem_size, &p), "HIPArray (deferred arithmetic)");
             ek_operand o[3];
             for (int k = 0; k < d->arity; ++k) {
                 HIPBuffer *b = d->operand_buf(k);
                 o[k] = d->is_imm[k] ? ek_operand{ nullptr, d->imm[k], 1 } : ek_operand{ b->ptr, 0, b->size };
             }
-            int rc = d->arity == 3 ? ek_hip_ternary(d->op, d->type, p, &o[0], &o[1], &o[2], size)
-                                   : ek_hip_binary(d->op, d->type, p, &o[0], &o[1], size);
-            if (rc != EK_OK) {
-                ek_hip_free(p);
-                hip_raise("HIPArray (deferred arithmetic)");
-            }
-            ptr = p;
-            drop_deferred();
-        }
-
-        /// kind 2 without an addend: the product of a gather with an array, the gather consumed in place (element order)
-        void force_gathered_product() {
-            Deferred *d = deferred;
-            void *p = nullptr;
-            hip_check(ek_hip_malloc((size ? size : 1) * d->elem_size, &p), "HIPArray (deferred product of a gather)");
-            ek_gathered g = gathered();
-            ek_operand x{ d->arg0->ptr, 0, d->arg0->size };
-            const ek_gathered *pg[3] = { &g, nullptr, nullptr };
-            const ek_operand *po[3] = { nullptr, &x, nullptr };
-            if (ek_hip_map_gathered(2, EK_MUL, d->type, p, po, pg, size) != EK_OK) {
-                ek_hip_free(p);
-                hip_raise("HIPArray (deferred product of a gather)");
-            }
-            ptr = p;
-            drop_deferred();
-        }
-
-        /// kind 2 with a host-scalar addend, element order: the fma family consumes the gather in place (one kernel); the operator
-        /// forms are the product that consumes the gather and the sum with the scalar behind it, in place -- the kernels and the
-        /// bits of the eager expression
-        void force_scalar_addend() {
-            Deferred *d = deferred;
-            void *p = nullptr;
-            hip_check(ek_hip_malloc((size ? size : 1) * d->elem_size, &p), "HIPArray (deferred fma of a gather and a scalar)");
-            ek_gathered g = gathered();
-            ek_operand x{ d->arg0->ptr, 0, d->arg0->size }, c{ d->addend ? d->addend->ptr : nullptr, d->addend ? 0 : d->imm[2], 1 };
-            const ek_gathered *pg[3] = { &g, nullptr, nullptr };
-            const ek_operand *po[3] = { nullptr, &x, &c };
-            int rc;
-            if (d->op == EK_MULADD || d->op == EK_MULSUB || d->op == EK_NMULADD) {
-                rc = ek_hip_map_gathered(2, EK_MUL, d->type, p, po, pg, size);
-                ek_operand prod{ p, 0, size };
-                if (rc == EK_OK)
-                    rc = d->op == EK_NMULADD ? ek_hip_binary(EK_SUB, d->type, p, &c, &prod, size)
-                                             : ek_hip_binary(d->op == EK_MULADD ? EK_ADD : EK_SUB, d->type, p, &prod, &c, size);
-            } else {
-                rc = ek_hip_map_gathered(3, d->op, d->type, p, po, pg, size);
-            }
-            if (rc != EK_OK) {
-                ek_hip_free(p);
-                hip_raise("HIPArray (deferred fma of a gather and a scalar)");
-            }
-            ptr = p;
-            drop_deferred();
+            evaluate("HIPArray (deferred arithmetic)", [&](void *p) {
+                return d->arity == 3 ? ek_hip_ternary(d->op, d->type, p, &o[0], &o[1], &o[2], size)
+                                     : ek_hip_binary(d->op, d->type, p, &o[0], &o[1], size);
+            });
         }
 
         /// Only the chain above holds / reads this unevaluated node: it can be recomputed inside the consumer instead of written
@@ -406,11 +376,11 @@ namespace detail {
         /// scale / partner of THIS node are its caller's business.
         void build_chain(ek_chain &ch, bool peek = false) {
             int ops[3], n = 0;
-            ops[n++] = deferred->index_type;
+            ops[n++] = deferred->map_op();
             HIPBuffer *src = deferred->table, *below = this;        // below: the node of the chain that reads src
             while (n < 3 && src->absorbable_() && src->deferred->kind == 1 && !src->deferred->scaled &&
                    !(src->deferred->partner && src->deferred->partner->deferred)) {
-                ops[n++] = src->deferred->index_type;
+                ops[n++] = src->deferred->map_op();
                 below = src;
                 src = src->deferred->table;
             }
@@ -438,22 +408,12 @@ namespace detail {
         /// like this (autodiff.cpp:332-338 zero-fills them); a bucket-ordered scatter_add that takes one as its target WRITES
         /// its sums instead of adding them to a memset buffer (adopt_uninitialized()), everybody else gets the memset.
         void force_zeros() {
-            void *p = nullptr;
             const size_t bytes = (size ? size : 1) * deferred->elem_size;
-            hip_check(ek_hip_malloc(bytes, &p), "HIPArray (zeros)");
-            if (ek_hip_memset(p, 0, bytes) != EK_OK) {
-                ek_hip_free(p);
-                hip_raise("HIPArray (zeros)");
-            }
-            ptr = p;
-            drop_deferred();
+            evaluate("HIPArray (zeros)", [&](void *p) { return ek_hip_memset(p, 0, bytes); });
         }
         /// Storage without contents for a pending zeros node whose only consumer is about to overwrite every entry
         void adopt_uninitialized() {
-            void *p = nullptr;
-            hip_check(ek_hip_malloc((size ? size : 1) * deferred->elem_size, &p), "HIPArray (zeros)");
-            ptr = p;
-            drop_deferred();
+            evaluate("HIPArray (zeros)", [](void *) { return (int) EK_OK; });
         }
 
         /// Execute the deferred gather / map
@@ -463,16 +423,10 @@ namespace detail {
             if (deferred->kind == 2) { force_pair(); return; }
             if (deferred->kind == 3) { force_zeros(); return; }
             if (deferred->kind == 4) { force_arith(); return; }
-            void *p = nullptr;
-            hip_check(ek_hip_malloc((size ? size : 1) * deferred->elem_size, &p), "HIPArray (deferred gather)");
             ek_gathered g = gathered();
-            int rc = ek_hip_gather(deferred->type, deferred->index_type, p, g.table, &g.index, &g.mask, size);
-            if (rc != EK_OK) {
-                ek_hip_free(p);
-                hip_raise("HIPArray (deferred gather)");
-            }
-            ptr = p;
-            drop_deferred();
+            evaluate("HIPArray (deferred gather)", [&](void *p) {
+                return ek_hip_gather(deferred->type, deferred->index_type, p, g.table, &g.index, &g.mask, size);
+            });
         }
 
         /// Deferred gathers that read this buffer must run before its contents change
@@ -487,18 +441,12 @@ namespace detail {
             pending_unlink();
             if (d->partner && d->partner->deferred) d->partner->deferred->partner = nullptr;
             if (d->bucketed) ek_hip_bucketed_destroy(d->bucketed);
-            for (HIPBuffer *src : { d->table, d->index, d->mask, d->table2, d->arg0, d->addend }) {
-                if (!src) continue;
+            d->each_source([this](HIPBuffer *src) {          // (a buffer in several slots: found among its readers the first time only)
                 auto &r = src->readers;
                 for (size_t i = 0; i < r.size(); ++i)
                     if (r[i] == this) { r[i] = r.back(); r.pop_back(); break; }
-            }
-            unref(d->table);
-            unref(d->index);
-            unref(d->mask);
-            unref(d->table2);
-            unref(d->arg0);
-            unref(d->addend);
+                unref(src);
+            });
             delete d;
         }
 
@@ -515,8 +463,6 @@ namespace detail {
         }
     };
 
-    /// Deferred evaluation (gathers and unary maps) can be switched off: ENOKI_HIP_DEFER=0 (or its first name,
-    /// ENOKI_HIP_DEFER_GATHER=0), or hip_set_defer(false) / hip_set_defer_gather(false)
     /// Deferred evaluation (gathers and unary maps) can be switched off: ENOKI_HIP_DEFER=0 (or its first name,
     /// ENOKI_HIP_DEFER_GATHER=0), or hip_set_defer(false) / hip_set_defer_gather(false).  One switch per process, whichever
     /// shared object asks.
@@ -872,12 +818,8 @@ template <typename Value_> struct HIPArray : ArrayTag {
             // sweep is to become the target of ONE scatter_add, which can then write instead of accumulate
             const size_t least = detail::hip_defer_min_override() ? detail::hip_defer_min_override() : defer_min_size_;
             if (detail::hip_defer_gather_flag() && size >= least) {
-                auto *d = new typename detail::HIPBuffer::Deferred{ nullptr, nullptr, nullptr, Type, 0, sizeof(Value), false, 3, nullptr };
                 HIPArray r;
-                r.m_buf = new detail::HIPBuffer();
-                r.m_buf->size = size;
-                r.m_buf->deferred = d;
-                r.m_buf->pending_link();
+                r.m_buf = detail::HIPBuffer::make_pending(new_node_(3), size);
                 return r;
             }
         }
@@ -1013,20 +955,62 @@ template <typename Value_> struct HIPArray : ArrayTag {
         if (n < least || n < 2 || source.m_buf->size * sizeof(Value) > defer_max_table_bytes_) return r;
         if (mask.m_is_imm ? !mask.m_imm : (!mask.m_buf || mask.m_buf->size != n || !mask.m_buf->owned || mask.m_buf->exported)) return r;
         source.ptr_();                                       // a table that is itself deferred runs first
-        auto *d = new typename detail::HIPBuffer::Deferred{ source.m_buf, index.m_buf, mask.m_is_imm ? nullptr : mask.m_buf,
-                                                            Type, Index::Type, sizeof(Value), false };
-        d->table->ref_count++;
-        d->index->ref_count++;
-        if (d->mask) d->mask->ref_count++;
-        r.m_buf = new detail::HIPBuffer();
-        r.m_buf->size = n;
-        r.m_buf->deferred = d;
-        r.m_buf->pending_link();
-        // every buffer the node will read hands out mutable pointers only after the node has run (data(), make_unique())
-        d->table->readers.push_back(r.m_buf);
-        if (d->index != d->table) d->index->readers.push_back(r.m_buf);
-        if (d->mask && d->mask != d->table && d->mask != d->index) d->mask->readers.push_back(r.m_buf);
+        auto *d = new_node_(0);
+        d->table = source.m_buf;
+        d->index = index.m_buf;
+        d->mask = mask.m_is_imm ? nullptr : mask.m_buf;
+        d->index_type = Index::Type;
+        r.m_buf = detail::HIPBuffer::make_pending(d, n);
         return r;
+    }
+
+    /// A node of the given kind for this element type, sources still to be filled in (detail::HIPBuffer::make_pending takes it)
+    static typename detail::HIPBuffer::Deferred *new_node_(int kind) {
+        auto *d = new typename detail::HIPBuffer::Deferred();
+        d->type = Type;
+        d->elem_size = sizeof(Value);
+        d->kind = kind;
+        return d;
+    }
+    /// The unevaluated unary map op(src) (kind 1; as long as its source)
+    static HIPArray map_node_(detail::HIPBuffer *src, int op, bool scaled = false, Value scale = Value(1)) {
+        auto *d = new_node_(1);
+        d->table = src;
+        d->index_type = op;
+        d->scaled = scaled;
+        if (scaled) d->scale_bits = imm_bits(scale);
+        HIPArray r;
+        r.m_buf = detail::HIPBuffer::make_pending(d, src->size);
+        return r;
+    }
+    /// The kind-2 node over the unevaluated gather `p` (its table, index, mask) and the array x: op(table[index], x, ...),
+    /// table2 / the scalar addend still to be filled in
+    static typename detail::HIPBuffer::Deferred *pair_node_(const typename detail::HIPBuffer::Deferred *p, detail::HIPBuffer *x, int op) {
+        auto *d = new_node_(2);
+        d->table = p->table;
+        d->index = p->index;
+        d->mask = p->mask;
+        d->index_type = p->index_type;
+        d->arg0 = x;
+        d->op = op;
+        return d;
+    }
+    /// What a kind-2 node asks of the array x next to the unevaluated gather `p` of n lookups: evaluated, owned, not exported, n
+    /// elements; masked gathers for 4-byte types only; a shape the library's bucket-ordered path covers.  `shape` names the
+    /// expression in the hip_set_log_level(2) note that says which one failed (nullptr: no note).
+    static bool pair_applicable_(const char *shape, const typename detail::HIPBuffer::Deferred *p, const HIPArray &x, size_t n) {
+        auto no = [shape](const char *why) {
+            if (shape) detail::hip_note_element_order(shape, why);
+            return false;
+        };
+        if (x.m_is_imm || !x.m_buf || x.m_buf->size != n) return no("x is a scalar / of another length");
+        if (!x.m_buf->owned || x.m_buf->exported) return no("x is a view of foreign memory or has a zero-copy export (an external writer could change it)");
+        if (x.m_buf->deferred) return no("x is itself unevaluated");
+        if (p->mask && sizeof(Value) != 4) return no("masked gathers of 8-byte elements");
+        if (!ek_hip_bucketed_applicable(Type, p->index_type, p->table->size, n))
+            return no("the library does not cover the shape (fewer than 2^18 lookups, a table within one bucket or beyond "
+                      "64 slices, deterministic mode, ENOKI_HIP_BUCKET_ORDERED=0)");
+        return true;
     }
 
     bool deferred_() const { return m_buf && m_buf->deferred && m_buf->deferred->kind == 0 && !m_buf->deferred->consumed; }
@@ -1047,28 +1031,8 @@ template <typename Value_> struct HIPArray : ArrayTag {
         HIPArray r;
         if constexpr (IsFloat) {
             const auto *p = g.m_buf->deferred;
-            if (!detail::hip_defer_gather_flag() || x.m_is_imm || !x.m_buf || x.m_buf->size != n || !x.m_buf->owned ||
-                x.m_buf->exported || x.m_buf->deferred || g.m_buf->size != n)
-                return r;
-            if (p->mask && sizeof(Value) != 4) return r;
-            if (!ek_hip_bucketed_applicable(Type, p->index_type, p->table->size, n)) return r;
-            auto *d = new typename detail::HIPBuffer::Deferred{ p->table, p->index, p->mask, Type, p->index_type, sizeof(Value),
-                                                                false, 2, nullptr };
-            d->arg0 = x.m_buf;
-            d->op = EK_MULADD;
-            r.m_buf = new detail::HIPBuffer();
-            r.m_buf->size = n;
-            r.m_buf->deferred = d;
-            r.m_buf->pending_link();
-            detail::HIPBuffer *seen[4] = { nullptr, nullptr, nullptr, nullptr };
-            int k = 0;
-            for (detail::HIPBuffer *src : { d->table, d->index, d->arg0, d->mask }) {
-                if (!src) continue;
-                src->ref_count++;
-                bool dup = false;
-                for (int j = 0; j < k; ++j) dup = dup || seen[j] == src;
-                if (!dup) { src->readers.push_back(r.m_buf); seen[k++] = src; }
-            }
+            if (!detail::hip_defer_gather_flag() || g.m_buf->size != n || !pair_applicable_(nullptr, p, x, n)) return r;
+            r.m_buf = detail::HIPBuffer::make_pending(pair_node_(p, x.m_buf, EK_MULADD), n);
             g.m_buf->deferred->consumed = true;
         }
         return r;
@@ -1135,36 +1099,11 @@ template <typename Value_> struct HIPArray : ArrayTag {
                 if (p->mask) { detail::hip_note_element_order(shape, "a size-1 device addend under a MASKED gather (a dropped lane's u is the scalar, which only the host-scalar kernels carry)"); return r; }
             }
             if (!cb && detail::HIPBuffer::shared().scalar_addend_off) { detail::hip_note_element_order(shape, "the scalar addend requires a gradient"); return r; }
-            if (p->kind != 2) {
-                if (x.m_is_imm || !xb || xb->size != n) { detail::hip_note_element_order(shape, "x is a scalar / of another length"); return r; }
-                if (!xb->owned || xb->exported) { detail::hip_note_element_order(shape, "x is a view of foreign memory or has a zero-copy export (an external writer could change it)"); return r; }
-                if (xb->deferred) { detail::hip_note_element_order(shape, "x is itself unevaluated"); return r; }
-                if (p->mask && sizeof(Value) != 4) { detail::hip_note_element_order(shape, "masked gathers of 8-byte elements"); return r; }
-                if (!ek_hip_bucketed_applicable(Type, p->index_type, p->table->size, n)) {
-                    detail::hip_note_element_order(shape, "the library does not cover the shape (fewer than 2^18 lookups, a table within one bucket or beyond "
-                                                          "64 slices, deterministic mode, ENOKI_HIP_BUCKET_ORDERED=0)");
-                    return r;
-                }
-            }
-            auto *d = new typename detail::HIPBuffer::Deferred{ p->table, p->index, p->mask, Type, p->index_type, sizeof(Value),
-                                                                false, 2, nullptr };
-            d->arg0 = xb;
-            d->op = op;
+            if (p->kind != 2 && !pair_applicable_(shape, p, x, n)) return r;
+            auto *d = pair_node_(p, xb, op);
             if (cb) d->addend = cb;
             else { d->is_imm[2] = true; d->imm[2] = imm_bits(c.m_imm); }
-            r.m_buf = new detail::HIPBuffer();
-            r.m_buf->size = n;
-            r.m_buf->deferred = d;
-            r.m_buf->pending_link();
-            detail::HIPBuffer *seen[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
-            int k = 0;
-            for (detail::HIPBuffer *src : { d->table, d->index, d->arg0, d->mask, d->addend }) {
-                if (!src) continue;
-                src->ref_count++;
-                bool dup = false;
-                for (int j = 0; j < k; ++j) dup = dup || seen[j] == src;
-                if (!dup) { src->readers.push_back(r.m_buf); seen[k++] = src; }
-            }
+            r.m_buf = detail::HIPBuffer::make_pending(d, n);
             if (p->kind != 2) g.m_buf->deferred->consumed = true;
         }
         return r;
@@ -1188,22 +1127,14 @@ template <typename Value_> struct HIPArray : ArrayTag {
                 any_array = true;
             }
             if (!any_array) return r;
-            auto *d = new typename detail::HIPBuffer::Deferred{ nullptr, nullptr, nullptr, Type, 0, sizeof(Value), false, 4, nullptr };
+            auto *d = new_node_(4);
             d->arity = arity;
             d->op = op;
-            r.m_buf = new detail::HIPBuffer();
-            r.m_buf->size = n;
-            r.m_buf->deferred = d;
-            r.m_buf->pending_link();
             for (int k = 0; k < arity; ++k) {
-                if (x[k]->m_is_imm) { d->is_imm[k] = true; d->imm[k] = imm_bits(x[k]->m_imm); continue; }
-                detail::HIPBuffer *b = x[k]->m_buf;
-                (k == 0 ? d->table : k == 1 ? d->arg0 : d->table2) = b;
-                b->ref_count++;
-                bool dup = false;
-                for (int j = 0; j < k; ++j) dup = dup || (!x[j]->m_is_imm && x[j]->m_buf == b);
-                if (!dup) b->readers.push_back(r.m_buf);
+                if (x[k]->m_is_imm) { d->is_imm[k] = true; d->imm[k] = imm_bits(x[k]->m_imm); }
+                else (k == 0 ? d->table : k == 1 ? d->arg0 : d->table2) = x[k]->m_buf;
             }
+            r.m_buf = detail::HIPBuffer::make_pending(d, n);
         }
         return r;
     }
@@ -1261,15 +1192,7 @@ template <typename Value_> struct HIPArray : ArrayTag {
             keep = depth <= 2;
         }
         if (!keep) ptr_();
-        auto *d = new typename detail::HIPBuffer::Deferred{ m_buf, nullptr, nullptr, Type, op, sizeof(Value), false, 1, nullptr };
-        m_buf->ref_count++;
-        HIPArray r;
-        r.m_buf = new detail::HIPBuffer();
-        r.m_buf->size = m_buf->size;
-        r.m_buf->deferred = d;
-        r.m_buf->pending_link();
-        m_buf->readers.push_back(r.m_buf);
-        return r;
+        return map_node_(m_buf, op);
     }
 
     /// factor * (this unevaluated map) as another unevaluated map of the same source (detail::HIPBuffer::Deferred::scale_bits).
@@ -1289,20 +1212,11 @@ template <typename Value_> struct HIPArray : ArrayTag {
                 // clear of the denormal range), when the first one is a power of two: the .5 rsqrt(u) that d/du sqrt(u) records
                 // times the seed of backward(c y)
                 int e2 = 0;
-                const bool pow2 = d->index_type == EK_RSQRT && std::fabs(std::frexp(old, &e2)) == Value(0.5) && e2 >= -32 && e2 <= 32;
+                const bool pow2 = d->map_op() == EK_RSQRT && std::fabs(std::frexp(old, &e2)) == Value(0.5) && e2 >= -32 && e2 <= 32;
                 if (old != Value(1) && old != Value(-1) && factor != Value(1) && factor != Value(-1) && !pow2) return r;
                 scale = old * factor;                 // exact
             }
-            detail::HIPBuffer *src = d->table;
-            auto *nd = new typename detail::HIPBuffer::Deferred{ src, nullptr, nullptr, Type, d->index_type, sizeof(Value), false, 1, nullptr };
-            nd->scaled = true;
-            nd->scale_bits = imm_bits(scale);
-            src->ref_count++;
-            r.m_buf = new detail::HIPBuffer();
-            r.m_buf->size = m_buf->size;
-            r.m_buf->deferred = nd;
-            r.m_buf->pending_link();
-            src->readers.push_back(r.m_buf);
+            r = map_node_(d->table, d->map_op(), true, scale);
         }
         return r;
     }
@@ -1316,21 +1230,12 @@ template <typename Value_> struct HIPArray : ArrayTag {
         if constexpr (IsFloat) {
             const auto *d = m_buf->deferred;
             int exponent = 0;
-            if (!detail::hip_defer_gather_flag() || d->index_type != EK_SQRT || d->scaled || !(numerator == numerator) ||
+            if (!detail::hip_defer_gather_flag() || d->map_op() != EK_SQRT || d->scaled || !(numerator == numerator) ||
                 numerator - numerator != Value(0) || numerator == Value(0))
                 return r;
             const Value mant = std::frexp(numerator, &exponent);
             if ((mant != Value(0.5) && mant != Value(-0.5)) || exponent < -32 || exponent > 32) return r;
-            detail::HIPBuffer *src = d->table;
-            auto *nd = new typename detail::HIPBuffer::Deferred{ src, nullptr, nullptr, Type, EK_RSQRT, sizeof(Value), false, 1, nullptr };
-            nd->scaled = numerator != Value(1);
-            nd->scale_bits = imm_bits(numerator);
-            src->ref_count++;
-            r.m_buf = new detail::HIPBuffer();
-            r.m_buf->size = m_buf->size;
-            r.m_buf->deferred = nd;
-            r.m_buf->pending_link();
-            src->readers.push_back(r.m_buf);
+            r = map_node_(d->table, EK_RSQRT, numerator != Value(1), numerator);
         }
         return r;
     }
@@ -1344,20 +1249,13 @@ template <typename Value_> struct HIPArray : ArrayTag {
             if (!detail::hip_defer_gather_flag() || !a.mapped_() || !b.mapped_()) return r;
             const auto *da = a.m_buf->deferred, *db = b.m_buf->deferred;
             if (da->table != db->table || da->scaled || db->scaled) return r;
-            const int oa = da->index_type, ob = db->index_type;
+            const int oa = da->map_op(), ob = db->map_op();
             int op = -1;
             if (a.m_buf == b.m_buf && oa == EK_RCP) op = EK_RCP_SQR;
             else if (a.m_buf == b.m_buf && oa == EK_RSQRT) op = EK_RSQRT_SQR;
             else if ((oa == EK_RSQRT && ob == EK_RSQRT_SQR) || (oa == EK_RSQRT_SQR && ob == EK_RSQRT)) op = EK_RSQRT_CUBE;
             if (op < 0) return r;
-            detail::HIPBuffer *src = da->table;
-            auto *nd = new typename detail::HIPBuffer::Deferred{ src, nullptr, nullptr, Type, op, sizeof(Value), false, 1, nullptr };
-            src->ref_count++;
-            r.m_buf = new detail::HIPBuffer();
-            r.m_buf->size = a.m_buf->size;
-            r.m_buf->deferred = nd;
-            r.m_buf->pending_link();
-            src->readers.push_back(r.m_buf);
+            r = map_node_(da->table, op);
         }
         return r;
     }
@@ -1380,33 +1278,10 @@ template <typename Value_> struct HIPArray : ArrayTag {
             const char *shape = "fma(gather(A, idx), x, gather(B, idx))";
             if (!detail::hip_defer_gather_flag()) return r;
             if (p->mask != q->mask) { detail::hip_note_element_order(shape, "the two gathers use different mask arrays"); return r; }
-            if (x.m_is_imm || !x.m_buf || x.m_buf->size != n) { detail::hip_note_element_order(shape, "x is a scalar / of another length"); return r; }
-            if (!x.m_buf->owned || x.m_buf->exported) { detail::hip_note_element_order(shape, "x is a view of foreign memory or has a zero-copy export (an external writer could change it)"); return r; }
-            if (x.m_buf->deferred) { detail::hip_note_element_order(shape, "x is itself unevaluated"); return r; }
-            if (p->mask && sizeof(Value) != 4) { detail::hip_note_element_order(shape, "masked gathers of 8-byte elements"); return r; }
-            if (!ek_hip_bucketed_applicable(Type, p->index_type, p->table->size, n)) {
-                detail::hip_note_element_order(shape, "the library does not cover the shape (fewer than 2^18 lookups, a table within one bucket or beyond "
-                                                      "64 slices, deterministic mode, ENOKI_HIP_BUCKET_ORDERED=0)");
-                return r;
-            }
-            auto *d = new typename detail::HIPBuffer::Deferred{ p->table, p->index, p->mask, Type, p->index_type, sizeof(Value),
-                                                                false, 2, nullptr };
+            if (!pair_applicable_(shape, p, x, n)) return r;
+            auto *d = pair_node_(p, x.m_buf, op);
             d->table2 = q->table;
-            d->arg0 = x.m_buf;
-            d->op = op;
-            r.m_buf = new detail::HIPBuffer();
-            r.m_buf->size = n;
-            r.m_buf->deferred = d;
-            r.m_buf->pending_link();
-            detail::HIPBuffer *seen[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
-            int k = 0;
-            for (detail::HIPBuffer *src : { d->table, d->index, d->table2, d->arg0, d->mask }) {
-                if (!src) continue;
-                src->ref_count++;
-                bool dup = false;
-                for (int j = 0; j < k; ++j) dup = dup || seen[j] == src;
-                if (!dup) { src->readers.push_back(r.m_buf); seen[k++] = src; }
-            }
+            r.m_buf = detail::HIPBuffer::make_pending(d, n);
             ga.m_buf->deferred->consumed = true;
             gc.m_buf->deferred->consumed = true;
         }
@@ -1426,7 +1301,7 @@ template <typename Value_> struct HIPArray : ArrayTag {
             detail::HIPBuffer *u = m->table;
             if (!u->deferred || !u->deferred->scalar_addend() || u->size <= 1) return r;
             const char *shape = "gradient of the scalar addend c of fma(gather(A, idx), x, c)";
-            if (!map_on_load_(m->index_type)) { detail::hip_note_element_order(shape, "the derivative is not a function the bucket-ordered kernels apply on load"); return r; }
+            if (!map_on_load_(m->map_op())) { detail::hip_note_element_order(shape, "the derivative is not a function the bucket-ordered kernels apply on load"); return r; }
             const Value factor = w.m_imm * g.map_scale_();
             // (safe_mul: a zero weight gives zero whatever g holds; a factor that is not finite keeps the lane-by-lane products)
             if (w.m_imm == Value(0)) {
@@ -1439,7 +1314,7 @@ template <typename Value_> struct HIPArray : ArrayTag {
             ek_hip_bucketed *b = u->bucketed();
             if (!b) { detail::hip_note_element_order(shape, "the library does not cover the shape (deterministic mode, ENOKI_HIP_BUCKET_ORDERED=0)"); return r; }
             r = empty_(1);
-            int rc = ek_hip_bucketed_addend_adjoint(b, m->index_type, imm_bits(factor), r.m_buf->ptr);
+            int rc = ek_hip_bucketed_addend_adjoint(b, m->map_op(), imm_bits(factor), r.m_buf->ptr);
             if (rc == EK_ERR_UNSUPPORTED) { detail::hip_note_element_order(shape, "the library does not cover the function"); return HIPArray(); }
             detail::hip_check(rc, "HIPArray (gradient of a scalar addend, bucket order)");
             if (ek_hip_log_level() >= 2)
@@ -1592,7 +1467,7 @@ template <typename Value_> struct HIPArray : ArrayTag {
             if constexpr (IsFloat) {
                 // an unevaluated unary result (the cos(u) of d/du sin(u), ...) is applied while the stream is loaded --
                 // unless a target is its own source buffer
-                if (values[c]->mapped_() && !values[c]->m_buf->deferred->scaled && map_on_load_(values[c]->m_buf->deferred->index_type)) {
+                if (values[c]->mapped_() && !values[c]->m_buf->deferred->scaled && map_on_load_(values[c]->m_buf->deferred->map_op())) {
                     const auto *d = values[c]->m_buf->deferred;
                     in_place = true;
                     for (size_t t = 0; t < count; ++t) {
@@ -1603,7 +1478,7 @@ template <typename Value_> struct HIPArray : ArrayTag {
                     if (in_place) {
                         if (d->table->deferred) d->table->force();      // the map of an unevaluated fma of gathers
                         ov[c] = ek_operand{ d->table->ptr, 0, d->table->size };
-                        ops[c] = d->index_type;
+                        ops[c] = d->map_op();
                         any_map = true;
                     }
                 }
@@ -1647,8 +1522,8 @@ template <typename Value_> struct HIPArray : ArrayTag {
             detail::HIPBuffer *src = nullptr;
             from_u[c] = 1; ops[c] = EK_COPY; imm[c] = 0;
             scale[c] = imm_bits(v.map_scale_());
-            if (v.mapped_() && !map_on_load_(v.m_buf->deferred->index_type)) return false;      // (a second-wave map: the bucket-ordered kernels do not carry it)
-            if (v.mapped_()) { src = v.m_buf->deferred->table; ops[c] = v.m_buf->deferred->index_type; }
+            if (v.mapped_() && !map_on_load_(v.m_buf->deferred->map_op())) return false;      // (a second-wave map: the bucket-ordered kernels do not carry it)
+            if (v.mapped_()) { src = v.m_buf->deferred->table; ops[c] = v.m_buf->deferred->map_op(); }
             else if (v.paired_()) src = v.m_buf;
             else if (v.m_is_imm) { from_u[c] = 0; imm[c] = imm_bits(v.m_imm); }
             else return false;
@@ -1687,7 +1562,7 @@ template <typename Value_> struct HIPArray : ArrayTag {
             // (`hsum(fnmadd(..))` itself, no map in between) -- u is then looked for among the readers of the WEIGHT's buffer
             // above, which for -x is the neg node's, not x's: no u, element order.
             const HIPArray &w = *weights[c];
-            if (!d->scalar_addend() || !w.mapped_() || w.m_buf->deferred->index_type != EK_NEG || w.m_buf->deferred->scaled ||
+            if (!d->scalar_addend() || !w.mapped_() || w.m_buf->deferred->map_op() != EK_NEG || w.m_buf->deferred->scaled ||
                 w.m_buf->deferred->table != d->arg0)
                 return false;
             Value sc;
@@ -1802,7 +1677,7 @@ template <typename Value_> struct HIPArray : ArrayTag {
                            (d->consumed ? " (a fused consumer has read it: the next access runs the gather kernel)"
                                         : ": add / sub / mul / fma consume it in place; fma (or `g * x + g2`) with a second gather through the SAME index "
                                           "array stays unevaluated for bucket order");
-            case 1: return std::string("unevaluated unary op ") + std::to_string(d->index_type) + (d->scaled ? " times a host scalar" : "") + ", " + n +
+            case 1: return std::string("unevaluated unary op ") + std::to_string(d->map_op()) + (d->scaled ? " times a host scalar" : "") + ", " + n +
                            ": reductions and scatter_add value streams apply it while loading; source " +
                            (d->table->deferred ? "unevaluated (kind " + std::to_string(d->table->deferred->kind) + ")" : "evaluated");
             case 2: return "unevaluated " + std::string(d->scalar_addend() ? (d->op >= EK_MULADD ? (d->addend ? "product of a gather with an array, then sum with a size-1 device addend" : "product of a gather with an array, then sum with a host scalar") : (d->addend ? "fma of a gather, an array and a size-1 device addend" : "fma of a gather, an array and a host scalar")) : !d->table2 ? "product of a gather with an array" : d->op >= EK_MULADD ? "product-then-sum of two gathers through one index array" : "fma of two gathers through one index array") + " (K = " +
@@ -1816,6 +1691,9 @@ template <typename Value_> struct HIPArray : ArrayTag {
             default: return "unevaluated (kind " + std::to_string(d->kind) + ")";
         }
     }
+
+    /// The buffer behind the handle, not owning (nullptr: a host scalar, or uninitialized) -- for the checkers of the bookkeeping
+    const detail::HIPBuffer *buffer_() const { return m_buf; }
 
     /// True when the array is a host-known scalar equal to `v` (lets callers skip `x * 1` style passes)
     bool is_literal_(Value v) const { return m_is_imm && m_imm == v; }
@@ -2227,13 +2105,13 @@ private:
                         int keep_op = EK_COPY, others = 0;
                         for (detail::HIPBuffer *rd : src->readers)
                             if (rd != m_buf && rd->deferred && rd->deferred->kind == 1 && rd->deferred->table == src) {
-                                keep_op = rd->deferred->index_type;
+                                keep_op = rd->deferred->map_op();
                                 ++others;
                             }
-                        if (others == 0 && m_buf->ref_count > 1) keep_op = d->index_type;
+                        if (others == 0 && m_buf->ref_count > 1) keep_op = d->map_op();
                         else if (others != 1) keep_op = EK_COPY;
                         // (a value that somebody else holds as well will be asked for again: u counts as held, too)
-                        if (reduce_bucketed_(src, op, d->index_type, r.m_buf->ptr, m_buf->ref_count > 1 ? 0 : 1, keep_op)) return finish();
+                        if (reduce_bucketed_(src, op, d->map_op(), r.m_buf->ptr, m_buf->ref_count > 1 ? 0 : 1, keep_op)) return finish();
                     }
                     if (src->deferred && (src->deferred->kind == 1 || src->deferred->kind == 4)) {
                         // maps over maps over an unevaluated arithmetic node: whatever only this chain wants is applied on load
@@ -2245,7 +2123,7 @@ private:
                         }
                     }
                     if (src->deferred) src->force();
-                    detail::hip_check(ek_hip_reduce_map(op, d->index_type, Type, r.m_buf->ptr, src->ptr, n), what);
+                    detail::hip_check(ek_hip_reduce_map(op, d->map_op(), Type, r.m_buf->ptr, src->ptr, n), what);
                     return finish();
                 }
             }
