@@ -423,7 +423,50 @@ extern "C" EK_API int ek_hip_partition_class_state(uint32_t *weights8, uint32_t 
 
 namespace ek {
 
+// Every partition that has left its first object (BucketPartition, ek_bucketed.h): the allocator's out-of-memory path asks here
+// for the storage of those that only a caller's handle keeps.
+static std::vector<BucketPartition *> &live_partitions() { static auto *v = new std::vector<BucketPartition *>(); return *v; }
+
+} // namespace ek
+void ek_hip_bucket_partition::free_storage() {
+    using namespace ek;
+    if (meta_slot >= 0) {
+        MetaRing &r = meta_ring();
+        r.busy[meta_slot] = false;
+        r.clean[meta_slot] = meta_clean;
+        meta_slot = -1;
+        meta = nullptr;
+    }
+    for (void **p : { &meta, &pair_idx, &x_b, &page_lists }) {
+        if (*p) ek_hip_free(*p);
+        *p = nullptr;
+    }
+}
+namespace ek {
+
+void partition_release(BucketPartition *p, bool object) {
+    if (!p) return;
+    if (object) p->objects--;
+    if (--p->refs) return;
+    auto &all = live_partitions();
+    for (size_t i = 0; i < all.size(); ++i)
+        if (all[i] == p) { all[i] = all.back(); all.pop_back(); break; }
+    delete p;
+}
+
+size_t evict_idle_partitions() {
+    size_t bytes = 0;
+    for (BucketPartition *p : live_partitions()) {
+        if (p->objects || p->evicted) continue;
+        bytes += p->positions * (sizeof(uint16_t) + sizeof(float));
+        p->free_storage();
+        p->evicted = true;
+    }
+    return bytes;
+}
+
 void release_meta_ring() {
+    evict_idle_partitions();           // (a cache's partitions keep ring blocks busy)
     ClassState &cs = class_state();
     if (cs.block) { ek_hip_free(cs.block); cs.block = nullptr; }
     MetaRing &r = meta_ring();
@@ -433,6 +476,14 @@ void release_meta_ring() {
 }
 
 Bucketed::~Bucketed() {
+    if (part) {
+        // the lists and the counter block are the partition's: it hears whether a reducing launch of this object left the counters zeroed
+        if (meta_clean) part->meta_clean = true;
+        meta = pair_idx = x_b = page_lists = nullptr;
+        meta_slot = -1;
+        partition_release(part, true);
+        part = nullptr;
+    }
     if (meta_slot >= 0) {
         MetaRing &r = meta_ring();
         r.busy[meta_slot] = false;
@@ -1566,6 +1617,7 @@ using namespace ek;
 struct ek_hip_bucketed : ek::Bucketed {
     std::vector<ek_hip_bucketed *> slices;
     void *addend_table = nullptr;    // owned: the addend table of an object made from a DEVICE scalar (ek_hip_bucketed_pair_create_scalar_device)
+    const void *partitioned[3] = { nullptr, nullptr, nullptr };   // index, x, mask as the creation saw them (ek_hip_bucketed_partition_retain asks where they live)
     size_t slice_span = 0;
     bool slices_split = false;       // the slices hold disjoint parts of the input (CoarseSplit) instead of filtered views of all of it
     ~ek_hip_bucketed() { for (ek_hip_bucketed *s : slices) delete s; if (addend_table) ek_hip_free(addend_table); }
@@ -1632,6 +1684,19 @@ int ek_hip_bucketed_pair_create_hinted(int type, int index_type, int op, const v
     return ek_hip_bucketed_pair_create_masked(type, index_type, op, table_a, table_c, table_size, x, index, nullptr, n, hints, out);
 }
 
+/// The bucket shift of a float table that ONE paged object covers, as the hints and the tuning select it; -1: the table is cut
+/// into slices.  (What an object asks of a partition it wants to stand on: the same shift, ek_hip_bucketed_pair_create_on.)
+static int paged_single_shift(size_t table_size, unsigned hints) {
+    const size_t bins = (size_t) bins_of<float>;
+    const bool adjoint = (hints & EK_BUCKETED_HINT_ADJOINT) && ctx().tuning.early_adjoint;
+    const bool want_half = adjoint && table_size <= (size_t) 2 * kMaxBuckets * (bins / 2);
+    if (table_size > (size_t) kMaxBuckets * (want_half ? bins / 2 : bins)) return -1;
+    const bool half = adjoint && table_size <= (size_t) kMaxBuckets * (bins / 2);
+    const bool quarter = half && (hints & EK_BUCKETED_HINT_BOUNDED) && early_fixed_enabled() &&
+                         table_size <= (size_t) kMaxBuckets * (bins / 4);
+    return bin_shift_of<float> - (half ? (quarter ? 2 : 1) : 0);
+}
+
 /// the object of op(A[index], x, C[index]) (addend == nullptr), or of op(A[index], x, *addend) with a host scalar (table_c == nullptr)
 /// bad_op: what an op outside the seven returns (the table entry points have always said "unsupported", the scalar one says "invalid")
 static int bucketed_pair_create(int type, int index_type, int op, const void *table_a, const void *table_c, const uint64_t *addend,
@@ -1648,6 +1713,7 @@ static int bucketed_pair_create(int type, int index_type, int op, const void *ta
     b->n = n; b->table_size = table_size;
     b->table_a = table_a; b->table_c = table_c;
     if (addend) { b->scalar_addend = true; b->addend_bits = *addend; }
+    b->partitioned[0] = index; b->partitioned[1] = x; b->partitioned[2] = mask;
     int rc;
     // valid int32 indices are non-negative: same bits as uint32
     // EK_BUCKETED_HINT_ADJOINT: buckets of half the size, so that a bucket's table slice AND its two gradient tables fit the LDS
@@ -1725,10 +1791,7 @@ static int bucketed_pair_create(int type, int index_type, int op, const void *ta
         } else {
             // EK_BUCKETED_HINT_BOUNDED on top of the adjoint hint: buckets of a QUARTER of the size (4 Ki entries), whose records and two planes
             // of 64-bit fixed-point sums fit the LDS (bucketed_early.hip) -- while the table is within kMaxBuckets of those
-            const bool quarter = half && (hints & EK_BUCKETED_HINT_BOUNDED) && early_fixed_enabled() &&
-                                 table_size <= (size_t) kMaxBuckets * (bins / 4);
-            const int down = half ? (quarter ? 2 : 1) : 0;
-            rc = bucketed_create_paged<uint32_t>(b, (const float *) x, (const uint32_t *) index, m, bin_shift_of<float> - down);
+            rc = bucketed_create_paged<uint32_t>(b, (const float *) x, (const uint32_t *) index, m, paged_single_shift(table_size, hints));
         }
     } else if (mask) {
         rc = fail(EK_ERR_UNSUPPORTED, "ek_hip_bucketed_pair_create_masked(): masks with 4-byte element types only");
@@ -1780,6 +1843,93 @@ int ek_hip_bucketed_pair_create_scalar_device(int type, int index_type, int op, 
     if (rc == EK_OK) rc = bucketed_pair_create(type, index_type, op, table_a, table, nullptr, table_size, x, index, nullptr, n, hints, out, EK_ERR_INVALID);
     if (rc != EK_OK) { ek_hip_free(table); return rc; }
     (*out)->addend_table = table;
+    return EK_OK;
+}
+
+int ek_hip_bucketed_partition_retain(ek_hip_bucketed *b, ek_hip_bucket_partition **out) {
+    if (!b || !out) return fail(EK_ERR_INVALID, "ek_hip_bucketed_partition_retain(): null pointer");
+    *out = nullptr;
+    // the single-object paged form, made outside a capture (a captured step's partition lives in the graph's pool and is refilled by
+    // every replay); quiet: "not available" is an answer, not an error
+    if (!ctx().tuning.partition_cache || b->type != EK_F32 || !b->slices.empty() || b->owner || b->meta_borrowed || !b->page_shift ||
+        b->win_span || !b->correct_masked || refuse_while_capturing_quiet() != EK_OK)
+        return EK_ERR_UNSUPPORTED;
+    // (an array that lives in a step graph's pool is rewritten by every replay of the graph, and nobody hears of it)
+    for (const void *src : b->partitioned)
+        if (src && graph_pool_owns(src)) return EK_ERR_UNSUPPORTED;
+    if (!b->part) {
+        // the storage changes hands: from here on the object stands on the partition like every later one
+        BucketPartition *p = new BucketPartition();
+        p->type = b->type; p->index_type = b->index_type; p->shift = b->shift;
+        p->n = b->n; p->table_size = b->table_size; p->has_mask = b->has_mask;
+        p->meta = b->meta; p->pair_idx = b->pair_idx; p->x_b = b->x_b; p->page_lists = b->page_lists;
+        p->meta_slot = b->meta_slot; p->meta_clean = false;
+        p->n_buckets = b->n_buckets; p->page_shift = b->page_shift; p->max_pieces = b->max_pieces; p->positions = b->positions;
+        p->bucket_base = b->bucket_base; p->piece_prefix = b->piece_prefix; p->base_part = b->base_part;
+        p->glist_full = b->glist_full; p->glist_part = b->glist_part;
+        p->active = b->active; p->ticket = b->ticket; p->reduce_partials = b->reduce_partials;
+        p->refs = p->objects = 1;
+        b->part = p;
+        live_partitions().push_back(p);
+        set_evict_hook(evict_idle_partitions);
+    }
+    b->part->refs++;
+    *out = b->part;
+    return EK_OK;
+}
+
+int ek_hip_bucket_partition_release(ek_hip_bucket_partition *p) {
+    partition_release(p, false);
+    return EK_OK;
+}
+
+int ek_hip_bucketed_pair_create_on(ek_hip_bucket_partition *p, int type, int index_type, int op, const void *table_a, const void *table_c,
+                                   const uint64_t *addend_bits, const void *addend_device, size_t table_size, size_t n, unsigned hints,
+                                   int has_mask, ek_hip_bucketed **out) {
+    if (int rc = ensure_init()) return rc;
+    if (!p || !out || !table_a) return fail(EK_ERR_INVALID, "ek_hip_bucketed_pair_create_on(): null pointer");
+    *out = nullptr;
+    if ((table_c != nullptr) + (addend_bits != nullptr) + (addend_device != nullptr) > 1)
+        return fail(EK_ERR_INVALID, "ek_hip_bucketed_pair_create_on(): more than one addend");
+    if (op != EK_FMADD && op != EK_FMSUB && op != EK_FNMADD && op != EK_FNMSUB && op != EK_MULADD && op != EK_MULSUB && op != EK_NMULADD)
+        return fail(EK_ERR_INVALID, "ek_hip_bucketed_pair_create_on(): op %d is neither of the fma family nor a product-then-sum", op);
+    if (!table_c && !addend_bits && !addend_device && op != EK_MULADD)
+        return fail(EK_ERR_INVALID, "ek_hip_bucketed_pair_create_on(): the product gather(A, idx) * x alone goes with EK_MULADD");
+    // quiet from here on: the caller partitions for itself
+    if (!ctx().tuning.partition_cache || p->evicted || refuse_while_capturing_quiet() != EK_OK) return EK_ERR_UNSUPPORTED;
+    if (type != p->type || index_type != p->index_type || table_size != p->table_size || n != p->n || (has_mask != 0) != p->has_mask ||
+        (addend_device && has_mask) || !ek_hip_bucketed_applicable(type, index_type, table_size, n) ||
+        paged_single_shift(table_size, hints) != p->shift)
+        return EK_ERR_UNSUPPORTED;
+    // (the object counts from here on: an allocation below that runs out of memory must not take this partition's storage back)
+    p->refs++; p->objects++;
+    void *table = nullptr;
+    if (addend_device) {
+        // (as ek_hip_bucketed_pair_create_scalar_device: the scalar, broadcast on the stream into a table the object owns)
+        int rc = ek_hip_malloc(table_size * sizeof(float), &table);
+        const ek_operand c{ addend_device, 0, 1 };
+        if (rc == EK_OK) rc = ek_hip_unary(EK_COPY, type, table, &c, table_size);
+        if (rc != EK_OK) {
+            if (table) ek_hip_free(table);
+            partition_release(p, true);
+            return rc;
+        }
+    }
+    ek_hip_bucketed *b = new ek_hip_bucketed();
+    b->type = type; b->index_type = index_type; b->op = op;
+    b->n = n; b->table_size = table_size;
+    b->table_a = table_a; b->table_c = table ? table : table_c;
+    b->addend_table = table;
+    if (addend_bits) { b->scalar_addend = true; b->addend_bits = *addend_bits; }
+    b->shift = p->shift; b->has_mask = p->has_mask;
+    b->n_buckets = p->n_buckets; b->page_shift = p->page_shift; b->max_pieces = p->max_pieces; b->positions = p->positions;
+    b->meta = p->meta; b->pair_idx = p->pair_idx; b->x_b = p->x_b; b->page_lists = p->page_lists;
+    b->meta_slot = p->meta_slot;
+    b->bucket_base = p->bucket_base; b->piece_prefix = p->piece_prefix; b->base_part = p->base_part;
+    b->glist_full = p->glist_full; b->glist_part = p->glist_part;
+    b->active = p->active; b->ticket = p->ticket; b->reduce_partials = p->reduce_partials;
+    b->part = p;
+    *out = b;
     return EK_OK;
 }
 

@@ -613,6 +613,41 @@ inline bool early_fixed_enabled() {
 }
 
 // ---- host side -------------------------------------------------------------------------------------
+// What the partition of (index, x, mask) produced, apart from any one expression: the bucket-ordered lists, the page directory
+// and the counter block with its result words.  A function of (index, x, mask, table size, bucket shift, page geometry) only --
+// not of the tables, the op or the addend -- so objects of several expressions, and of several steps, stand on ONE partition
+// (ek_hip_bucketed_partition_retain / ek_hip_bucketed_pair_create_on).  Nobody writes into what it owns once it is built, except
+// the finish ticket and the reduce partials of `meta`: per launch, and launches are ordered by the one stream.
+// Single-object paged form only (4-byte element types, no slices).  (The C ABI's handle type: declared outside the namespace.)
+} // namespace ek
+struct ek_hip_bucket_partition {
+    uint32_t refs = 0;             // objects built on it + handles given out
+    uint32_t objects = 0;          // ... of which objects: 0 = only handles (a cache) hold it, the allocator may evict it
+    bool evicted = false;          // the storage went back to the allocator (out of memory): create_on answers EK_ERR_UNSUPPORTED
+    int type = 0, index_type = 0, shift = 0;
+    size_t n = 0, table_size = 0;
+    bool has_mask = false;
+    // storage (taken over from the object whose creation ran the partition)
+    void *meta = nullptr, *pair_idx = nullptr, *x_b = nullptr, *page_lists = nullptr;
+    int meta_slot = -1;
+    bool meta_clean = false;       // a reducing launch of SOME object on it ran: the counters of the ring block are zero
+    // geometry and views into the storage
+    int n_buckets = 0, page_shift = 0;
+    unsigned max_pieces = 0;
+    size_t positions = 0;
+    uint32_t *bucket_base = nullptr, *piece_prefix = nullptr, *base_part = nullptr, *glist_full = nullptr, *glist_part = nullptr;
+    const uint32_t *active = nullptr;
+    uint32_t *ticket = nullptr;
+    void *reduce_partials = nullptr;
+    void free_storage();           // bucketed.hip: the ring block back to the ring (with its `clean` state), the rest to the allocator
+    ~ek_hip_bucket_partition() { free_storage(); }
+};
+namespace ek {
+using BucketPartition = ::ek_hip_bucket_partition;
+void partition_release(BucketPartition *p, bool object);      // bucketed.hip
+size_t evict_idle_partitions();                               // ... the storage of every partition no object stands on goes back to the
+                                                              // allocator (set_evict_hook(), ek_internal.h); bytes given back
+
 struct Bucketed {
     int type = 0, index_type = 0, op = 0;
     size_t n = 0, table_size = 0;
@@ -655,6 +690,7 @@ struct Bucketed {
     bool correct_masked = true;            // the final reduction adds the masked-out lanes' map_op(0) terms (slices: their owner does)
     Bucketed *owner = nullptr;             // a slice of a split table: pair_idx / x_b / u_b / m_b are the owner's page pool (not owned)
     bool meta_borrowed = false;            // ... whose counter block and glist_part are parts of ONE allocation of the caller (PagedSlice::meta)
+    BucketPartition *part = nullptr;       // meta / pair_idx / x_b / page_lists and the views into them are the partition's (a reference held)
 
     bool has_mask = false;
     // (with or without a mask array: lanes whose index points outside the table are dropped by the partition too, and count like

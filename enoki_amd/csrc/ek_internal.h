@@ -33,6 +33,8 @@ struct Tuning {
     int gather_records = 1;       // struct gathers through staged {x, y, ..} records: 1 by size, 2 always, 0 never
     int bucket_ordered = 1;       // gather -> fma -> {reduction, scatter_add} chains in bucket order (bucketed.hip); 0: element order only
     int early_adjoint = 1;        // EK_BUCKETED_HINT_ADJOINT is honoured (half-size buckets, adjoint sums formed in the forward pass)
+    int partition_cache = 1;      // a bucket partition may be kept by its caller and stood on again (ek_hip_bucketed_partition_retain /
+                                  // ek_hip_bucketed_pair_create_on); 0: both answer EK_ERR_UNSUPPORTED, every object partitions for itself
     int xcd_balance = 0;          // 1: the page partition deals its tiles to the workgroup classes w % 8 by fed-back weights (ek_paged.h);
                                   // 2: equal chunks, but the classes' loop durations are recorded (ek_hip_partition_class_state)
 };
@@ -163,6 +165,9 @@ int scatter_add_binned(T *base, size_t table_size, const Arg<T> &value, const Ar
 int refuse_while_capturing(const char *what);
 int refuse_while_capturing_quiet();        // EK_OK when no capture is in progress; sets no error message
 void release_meta_ring();                  // bucketed.hip: the context's counter blocks go back to the allocator (device switch)
+bool graph_pool_owns(const void *ptr);     // runtime.cpp: the block (an ek_hip_malloc() result) belongs to a step graph's private pool
+void set_evict_hook(size_t (*hook)());     // runtime.cpp: called by ek_hip_malloc() when the device is out of memory, before the cache is trimmed;
+                                           // returns the bytes it gave back (bucketed.hip registers evict_idle_partitions())
 
 // The unary ops that a consumer may apply on load (HIPArray defers exactly these: include/enoki/hip.h)
 constexpr inline bool unary_fusable(int op) {

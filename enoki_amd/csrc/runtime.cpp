@@ -90,6 +90,17 @@ static Allocator &alloc() {
     return *a;
 }
 
+// Whoever keeps device memory that it can do without (bucketed.hip: bucket partitions that only a cache holds) registers here;
+// ek_hip_malloc() calls it, without the allocator's lock, before it trims the cache and tries again.
+static size_t (*g_evict_hook)() = nullptr;
+void set_evict_hook(size_t (*hook)()) { g_evict_hook = hook; }
+
+bool graph_pool_owns(const void *ptr) {
+    Allocator &a = alloc();
+    std::lock_guard<std::mutex> guard(a.mutex);
+    return a.pool_of.count(const_cast<void *>(ptr)) != 0;
+}
+
 int ensure_init() {
     if (ctx().initialized) return EK_OK;
     return ek_hip_init(-1);
@@ -231,6 +242,7 @@ int ek_hip_init(int device) {
     if (const char *dv = getenv("ENOKI_HIP_DETERMINISTIC")) c.tuning.deterministic = atoi(dv) != 0;
     if (const char *bo = getenv("ENOKI_HIP_BUCKET_ORDERED")) c.tuning.bucket_ordered = atoi(bo) != 0;
     if (const char *ea = getenv("ENOKI_HIP_EARLY_ADJOINT")) c.tuning.early_adjoint = atoi(ea) != 0;
+    if (const char *pc = getenv("ENOKI_HIP_PARTITION_CACHE")) c.tuning.partition_cache = atoi(pc) != 0;
     if (const char *xb = getenv("ENOKI_HIP_XCD_BALANCE")) c.tuning.xcd_balance = atoi(xb) == 2 ? 2 : atoi(xb) != 0;
     if (const char *gr = getenv("ENOKI_HIP_GATHER_RECORDS")) { int v = atoi(gr); if (v >= 0 && v <= 2) c.tuning.gather_records = v; }
     if (c.log_level >= 1)
@@ -276,7 +288,7 @@ int ek_hip_malloc(size_t bytes, void **out) {
     if (rc) return rc;
     Allocator &a = alloc();
     size_t cls = Allocator::round_size(bytes);
-    std::lock_guard<std::mutex> guard(a.mutex);
+    std::unique_lock<std::mutex> guard(a.mutex);
     void *ptr = nullptr;
     GraphPool *pool = a.capture_pool;
     if (pool) {
@@ -303,6 +315,10 @@ int ek_hip_malloc(size_t bytes, void **out) {
             // being captured: fail cleanly instead
             if (int busy = refuse_while_capturing("ek_hip_malloc(): out of device memory, and trimming the cache")) return busy;
             hipError_t e2 = hipStreamSynchronize(ctx().stream);
+            // (bucket partitions that only a cache holds give their storage back first: their frees take this lock)
+            guard.unlock();
+            if (g_evict_hook) g_evict_hook();
+            guard.lock();
             if (e2 == hipSuccess) e2 = a.trim_locked();
             if (e2 == hipSuccess) e = hipMalloc(&ptr, cls);
             if (e != hipSuccess) {
@@ -618,6 +634,7 @@ int ek_hip_set_tuning(const char *key, int value) {
     else if (!strcmp(key, "gather_records") && value >= 0 && value <= 2) t.gather_records = value;
     else if (!strcmp(key, "bucket_ordered") && (value == 0 || value == 1)) t.bucket_ordered = value;
     else if (!strcmp(key, "early_adjoint") && (value == 0 || value == 1)) t.early_adjoint = value;
+    else if (!strcmp(key, "partition_cache") && (value == 0 || value == 1)) t.partition_cache = value;
     else if (!strcmp(key, "xcd_balance") && value >= 0 && value <= 2) t.xcd_balance = value;
     else return fail(EK_ERR_INVALID, "ek_hip_set_tuning(): unknown key/value %s=%d", key, value);
     return EK_OK;

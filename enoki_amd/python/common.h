@@ -112,7 +112,7 @@ template <typename Array> py::class_<Array> bind_array(py::module_ &m, const cha
           uintptr_t ptr = py::tuple(d["data"])[0].cast<uintptr_t>();
           sync_with_torch();
           Plain r = empty<Plain>(n);
-          if (n) detail::hip_check(ek_hip_memcpy_device(r.data(), (const void *) ptr, n * sizeof(Store)), "copy from device object");
+          if (n) detail::hip_check(ek_hip_memcpy_device(r.fill_ptr_(), (const void *) ptr, n * sizeof(Store)), "copy from device object");
           return Array(r);
       }))
       .def("torch", [](Array &a) {

@@ -39,6 +39,11 @@ namespace detail {
         if (ek_hip_log_level() >= 2) fprintf(stderr, "enoki-hip: [bucket order] %s: %s\n", what, why);
     }
 
+    /// ... and, at the same level, one line whenever a kept bucket partition is stood on again or let go (HIPBuffer::PartitionEntry)
+    inline void hip_note_partition_cache(const char *what, const char *why) {
+        if (ek_hip_log_level() >= 2) fprintf(stderr, "enoki-hip: [partition cache] %s: %s\n", what, why);
+    }
+
     /// Reference-counted device allocation
     ///
     /// A buffer may be a *deferred gather*: `table[index]` under `mask` that has not been executed yet (ptr == nullptr).
@@ -198,6 +203,45 @@ namespace detail {
         void leave_narrowed_cache() { if (narrowed_of) narrowed_of->drop_narrowed(); }
         void *host_mirror = nullptr;           // begin() / end(): read-only host copy, dropped when the buffer may change
         bool exported = false;                 // an external zero-copy view (torch, __cuda_array_interface__) may exist
+        // A mutable pointer (non-const data(), python's data_ptr()) or a zero-copy export has EVER been handed out: the holder may
+        // write at any time without telling anyone, so nothing derived from the contents is kept across calls any more (sticky)
+        bool handed_out = false;
+
+        // The bucket partition of a kind-2 node depends on (index, x, mask), the table size and the bucket size the hints select --
+        // not on the tables, the op or the addend.  In a fit the tables change every step and the lookups do not, so the partition
+        // of the last node stays on its INDEX buffer (at most one per buffer, like `narrowed`; a 64-bit index array: on its
+        // narrowed copy) for as long as the contents of all three cannot change, and the next node over the same three stands on
+        // it without a launch (ek_hip_bucketed_pair_create_on).  The entry owns a handle on the partition and NOTHING else: no
+        // reference on index, x or mask (make_unique(), absorbable_() and only_sibling_maps_() read ref_count) -- it stands in
+        // `partition_uses` of x and mask the way a node stands in `readers`, and whichever of the three is destroyed, handed out
+        // or about to be written first takes it down (drop_partition_cache(), called wherever drop_narrowed() is).
+        struct PartitionEntry {
+            ek_hip_bucket_partition *part = nullptr;
+            HIPBuffer *index = nullptr, *x = nullptr, *mask = nullptr;      // not owning
+            size_t table_size = 0;
+            int type = 0, index_type = 0;
+            unsigned hints = 0;
+        };
+        PartitionEntry *partition_entry = nullptr;          // this buffer is the entry's index array (owning)
+        std::vector<PartitionEntry *> partition_uses;       // entries whose x or mask is this buffer (not owning)
+        static void drop_partition_entry(PartitionEntry *e, const char *why) {
+            hip_note_partition_cache("entry dropped", why);
+            e->index->partition_entry = nullptr;
+            for (HIPBuffer *b : { e->x, e->mask }) {
+                if (!b) continue;
+                auto &u = b->partition_uses;
+                for (size_t i = 0; i < u.size();)
+                    if (u[i] == e) { u[i] = u.back(); u.pop_back(); } else ++i;
+            }
+            ek_hip_bucket_partition_release(e->part);
+            delete e;
+        }
+        void drop_partition_cache(const char *why) {
+            if (partition_entry) drop_partition_entry(partition_entry, why);
+            while (!partition_uses.empty()) drop_partition_entry(partition_uses.back(), why);
+        }
+        /// May this buffer be the index, x or mask of an entry?  Evaluated, owned storage that nobody outside holds a pointer to
+        bool partition_cacheable_() const { return ptr && owned && !deferred && !view_of && !exported && !handed_out; }
 
         static void unref(HIPBuffer *b) {
             if (b && --b->ref_count == 0) delete b;
@@ -317,28 +361,61 @@ namespace detail {
             });
         }
 
-        /// The bucket partition of a kind-2 node (built on first use); nullptr when the library does not cover the shape
+        /// The bucket partition of a kind-2 node (built on first use, or found on the index array: PartitionEntry); nullptr when the
+        /// library does not cover the shape
         ek_hip_bucketed *bucketed(unsigned hints = 0) {
             Deferred *d = deferred;
-            if (!d->bucketed && d->scalar_addend()) {
-                // (EK_OPTIONAL in enoki_hip.h: a C ABI that predates the entry, or a host stand-in of it, leaves the address null --
-                //  "shape not covered", the expression runs in element order with the same bits)
-                if (d->addend ? !&ek_hip_bucketed_pair_create_scalar_device : !&ek_hip_bucketed_pair_create_scalar) return nullptr;
-                int rc = d->addend
+            if (d->bucketed) return d->bucketed;
+            // (EK_OPTIONAL in enoki_hip.h: a C ABI that predates the entry, or a host stand-in of it, leaves the address null --
+            //  "shape not covered", the expression runs in element order with the same bits)
+            if (d->scalar_addend() && (d->addend ? !&ek_hip_bucketed_pair_create_scalar_device : !&ek_hip_bucketed_pair_create_scalar)) return nullptr;
+            const uint8_t *mask_ptr = d->mask ? (const uint8_t *) d->mask->ptr : nullptr;
+            // (the same way: without the partition entries of the C ABI every node partitions for itself)
+            const bool cacheable = &ek_hip_bucketed_partition_retain && &ek_hip_bucket_partition_release && &ek_hip_bucketed_pair_create_on &&
+                                   d->index->partition_cacheable_() && d->arg0->partition_cacheable_() && (!d->mask || d->mask->partition_cacheable_());
+            if (cacheable && d->index->partition_entry) {
+                PartitionEntry *e = d->index->partition_entry;
+                if (e->x == d->arg0 && e->mask == d->mask && e->table_size == d->table->size && e->type == d->type &&
+                    e->index_type == d->index_type && e->hints == hints) {
+                    const bool host_scalar = d->scalar_addend() && !d->addend;
+                    int rc = ek_hip_bucketed_pair_create_on(e->part, d->type, d->index_type, d->op, d->table->ptr, d->table2 ? d->table2->ptr : nullptr,
+                                                            host_scalar ? &d->imm[2] : nullptr, d->addend ? d->addend->ptr : nullptr,
+                                                            d->table->size, size, hints, d->mask ? 1 : 0, &d->bucketed);
+                    if (rc == EK_OK) {
+                        hip_note_partition_cache("partition reused", "index, x and mask arrays, table size and hints are those of the kept partition");
+                        return d->bucketed;
+                    }
+                    if (rc != EK_ERR_UNSUPPORTED) hip_check(rc, "HIPArray (bucket partition)");
+                    drop_partition_entry(e, "the library does not stand an object on it (evicted for memory, a step graph is being captured, or switched off)");
+                }
+            }
+            int rc;
+            if (d->scalar_addend())
+                rc = d->addend
                     ? ek_hip_bucketed_pair_create_scalar_device(d->type, d->index_type, d->op, d->table->ptr, d->addend->ptr, d->table->size,
-                                                                d->arg0->ptr, d->index->ptr, d->mask ? (const uint8_t *) d->mask->ptr : nullptr,
-                                                                size, hints, &d->bucketed)
+                                                                d->arg0->ptr, d->index->ptr, mask_ptr, size, hints, &d->bucketed)
                     : ek_hip_bucketed_pair_create_scalar(d->type, d->index_type, d->op, d->table->ptr, d->imm[2], d->table->size, d->arg0->ptr,
-                                                         d->index->ptr, d->mask ? (const uint8_t *) d->mask->ptr : nullptr, size, hints,
-                                                         &d->bucketed);
-                if (rc == EK_ERR_UNSUPPORTED) return nullptr;
-                hip_check(rc, "HIPArray (bucket partition)");
-            } else if (!d->bucketed) {
-                int rc = ek_hip_bucketed_pair_create_masked(d->type, d->index_type, d->op, d->table->ptr, d->table2 ? d->table2->ptr : nullptr, d->table->size,
-                                                            d->arg0->ptr, d->index->ptr, d->mask ? (const uint8_t *) d->mask->ptr : nullptr,
-                                                            size, hints, &d->bucketed);
-                if (rc == EK_ERR_UNSUPPORTED) return nullptr;
-                hip_check(rc, "HIPArray (bucket partition)");
+                                                         d->index->ptr, mask_ptr, size, hints, &d->bucketed);
+            else
+                rc = ek_hip_bucketed_pair_create_masked(d->type, d->index_type, d->op, d->table->ptr, d->table2 ? d->table2->ptr : nullptr, d->table->size,
+                                                        d->arg0->ptr, d->index->ptr, mask_ptr, size, hints, &d->bucketed);
+            if (rc == EK_ERR_UNSUPPORTED) return nullptr;
+            hip_check(rc, "HIPArray (bucket partition)");
+            if (cacheable) {
+                // keep what was just built (the library says no to sliced tables, 8-byte types, a step that is being captured, the switch):
+                // a miss replaces the entry, the old partition lives until its last object is gone
+                ek_hip_bucket_partition *part = nullptr;
+                if (ek_hip_bucketed_partition_retain(d->bucketed, &part) == EK_OK && part) {
+                    if (d->index->partition_entry)
+                        drop_partition_entry(d->index->partition_entry, "another x, mask, table size or hint set over the same index array");
+                    PartitionEntry *e = new PartitionEntry();
+                    e->part = part;
+                    e->index = d->index; e->x = d->arg0; e->mask = d->mask;
+                    e->table_size = d->table->size; e->type = d->type; e->index_type = d->index_type; e->hints = hints;
+                    d->index->partition_entry = e;
+                    d->arg0->partition_uses.push_back(e);
+                    if (d->mask) d->mask->partition_uses.push_back(e);
+                }
             }
             return d->bucketed;
         }
@@ -433,6 +510,7 @@ namespace detail {
         void force_readers() {
             while (!readers.empty()) readers.back()->force();
             drop_narrowed();                   // (called whenever the contents may change)
+            drop_partition_cache("the index, x or mask array is about to be written, exported or handed out as a mutable pointer");
         }
 
         void drop_deferred() {
@@ -457,6 +535,7 @@ namespace detail {
         ~HIPBuffer() {
             if (deferred) drop_deferred();
             drop_narrowed();
+            drop_partition_cache("the index, x or mask array is gone");
             drop_host_mirror();
             if (owned && ptr) ek_hip_free(ptr);
             unref(view_of);
@@ -1602,6 +1681,7 @@ template <typename Value_> struct HIPArray : ArrayTag {
         if (!m_buf) return;
         m_buf->force_readers();                // unevaluated nodes that read this buffer must see it as it is NOW
         m_buf->exported = true;
+        m_buf->handed_out = true;
         // an external view may write: neither a narrowed copy OF this buffer nor this buffer AS somebody's narrowed copy stays valid
         m_buf->drop_narrowed();
         m_buf->leave_narrowed_cache();
@@ -1706,10 +1786,15 @@ template <typename Value_> struct HIPArray : ArrayTag {
         materialize();
         if (!m_buf) return nullptr;
         m_buf->force_readers();                // the caller may write through the pointer
+        m_buf->handed_out = true;              // ... now or at any later time
         m_buf->leave_narrowed_cache();
         m_buf->drop_host_mirror();
         return (Value *) ptr_();
     }
+
+    /// The storage of an array that was JUST created (empty_()), for the library call that fills it.  No pointer leaves the binding, so
+    /// this is not a hand-out: the array can still be the index, x or mask of a kept partition (detail::HIPBuffer::PartitionEntry)
+    Value *fill_ptr_() { return m_buf ? (Value *) ptr_() : nullptr; }
 
     /// Host-side iteration `for (float v : array)` (the reference's CUDAArray iterates its managed memory, cuda.h:945-949):
     /// a read-only host copy made on first use (synchronises); discarded when a mutable pointer is handed out
@@ -2079,7 +2164,7 @@ private:
         size_t n = broadcast_size(size(), b.size());
         MaskType r = MaskType::empty_(n);
         ek_operand oa = operand(), ob = b.operand();
-        detail::hip_check(ek_hip_compare(op, Type, (uint8_t *) r.data(), &oa, &ob, n), what);
+        detail::hip_check(ek_hip_compare(op, Type, (uint8_t *) r.fill_ptr_(), &oa, &ob, n), what);
         return r;
     }
 

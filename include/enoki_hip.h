@@ -167,7 +167,7 @@ EK_API int ek_hip_graph_end(ek_hip_graph **out);
 EK_API int ek_hip_graph_launch(ek_hip_graph *graph);
 EK_API uint64_t ek_hip_graph_launch_count(const ek_hip_graph *graph);   /* kernel launches inside one replay */
 EK_API int ek_hip_graph_destroy(ek_hip_graph *graph);
-EK_API int ek_hip_set_tuning(const char *key, int value);   /* "reduce_blocks_per_cu", "scatter_add_binned", "deterministic", "gather_records", "bucket_ordered", "early_adjoint" */
+EK_API int ek_hip_set_tuning(const char *key, int value);   /* "reduce_blocks_per_cu", "scatter_add_binned", "deterministic", "gather_records", "bucket_ordered", "early_adjoint", "partition_cache" */
 /* Per-kernel timing: between begin and end one HIP event is recorded on the library stream after every
    launch.  ek_hip_profile_end() synchronizes and returns a malloc'd JSON array (caller free()s) of
    {"kernel", "launches", "total_ms", "bytes", "elements"}; `bytes` are the ALGORITHMIC bytes of the
@@ -384,6 +384,28 @@ EK_API int ek_hip_bucketed_early_pair(int map_op, int keep_op);
  * is being captured. */
 EK_API int ek_hip_bucketed_piece_counts(ek_hip_bucketed *b, uint32_t *pieces, uint32_t *largest);
 EK_API int ek_hip_bucketed_destroy(ek_hip_bucketed *b);
+/* The PARTITION of an object -- the bucket-ordered lists of (index, x, mask), the page directory, the counts -- depends on (index, x,
+ * mask, table size, the bucket size the hints select) only: not on the tables, the op or the addend.  A caller whose index, x and
+ * mask arrays keep their contents from step to step (a fit over fixed connectivity: the tables change, the lookups do not) keeps it
+ * and stands every later object on it; such an object costs no launch and only its per-expression state (kept u, early sums).
+ * partition_retain: a counted handle on the partition of an object that has JUST been created.  partition_release gives it back; the
+ *   storage lives until the last object on it and the last handle are gone.  Any number of objects may be alive on one partition.
+ * pair_create_on: the object of op(A[index], x, addend) on an existing partition.  table_c / addend_bits / addend_device: the addend
+ *   table, a host scalar (bits of the element type), one element in device memory (broadcast into a table the object owns: one launch,
+ *   as ek_hip_bucketed_pair_create_scalar_device) -- at most one; none: the product alone (EK_MULADD).  The caller vouches that index,
+ *   x and mask hold what they held when the partition was built.
+ * Both answer EK_ERR_UNSUPPORTED -- without an error message: the caller partitions for itself -- for anything but the single-object
+ * paged form (4-byte element types, tables of one slice), while a step graph is being captured (a captured step's partition is part
+ * of the graph; so is an index, x or mask array that lives in a graph's pool: every replay rewrites it), and with the tuning "partition_cache" = 0 (ENOKI_HIP_PARTITION_CACHE=0).  pair_create_on also when type, index type,
+ * table size, n, mask presence or the bucket size that `hints` select differ from the partition's, and when the partition was
+ * EVICTED: an allocation that runs out of device memory takes back the storage of partitions that no object stands on.
+ * EK_OPTIONAL: enoki/hip.h asks for the entries' addresses first and partitions every step without them. */
+typedef struct ek_hip_bucket_partition ek_hip_bucket_partition;
+EK_API EK_OPTIONAL int ek_hip_bucketed_partition_retain(ek_hip_bucketed *b, ek_hip_bucket_partition **out);
+EK_API EK_OPTIONAL int ek_hip_bucket_partition_release(ek_hip_bucket_partition *p);
+EK_API EK_OPTIONAL int ek_hip_bucketed_pair_create_on(ek_hip_bucket_partition *p, int type, int index_type, int op, const void *table_a,
+                                              const void *table_c, const uint64_t *addend_bits, const void *addend_device,
+                                              size_t table_size, size_t n, unsigned hints, int has_mask, ek_hip_bucketed **out);
 /* ---- multi-GPU without python / torch (csrc/dist.cpp) -------------------------------------------------------------------------
  * One process per GPU.  Index-range sharding: rank r owns [r n / P, (r + 1) n / P) of EVERY size-n array (ek_hip_dist_shard_range),
  * so all vertical operations are local; size-1 arrays and gather tables are replicated.  The exchange steps -- a horizontal result,

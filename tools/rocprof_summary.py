@@ -34,10 +34,14 @@ def kernels(d):
         rows = list(cur.execute("select name, total_calls, total_duration, average, percentage from top_kernels"))
         for name, calls, total, avg, pct in rows:
             print(f"{short(name):112s} {calls:6d} {total:12.1f} {avg:10.2f} {pct:7.2f}")
-        # one step of the profiled workload = one launch of the partition kernel (bucket-ordered workloads): every kernel that is
+        # one step of the profiled workload = one launch of the forward + adjoint kernel (bucket-ordered workloads; the partition
+        # kernel, which used to be counted here, runs once per PROCESS since index / x / mask arrays that do not change keep their
+        # partition -- a trace without the forward + adjoint kernel is counted by the partition as before): every kernel that is
         # launched at least once per step, summed over ALL its launches and divided by the number of steps -- what the kernels of one
-        # step take back to back on an in-order stream (bench.py compares its ms_per_step with this: trace_check)
-        steps = max((calls for name, calls, *_ in rows if "k_page_partition" in name), default=0)
+        # STEADY-STATE step take back to back on an in-order stream (bench.py compares its ms_per_step with this: trace_check)
+        steps = max((calls for name, calls, *_ in rows if "k_bucket_pair_forward_adjoint" in name), default=0)
+        if not steps:
+            steps = max((calls for name, calls, *_ in rows if "k_page_partition" in name), default=0)
         if steps:
             per_step = sum(total for name, calls, total, *_ in rows if calls >= steps) / steps
             print(f"# steps: {steps}")
