@@ -48,6 +48,7 @@ EXPORTS = [
     "ek_hip_dist_reduce_scatter", "ek_hip_dist_all_gather", "ek_hip_dist_finalize", "ek_hip_dist_rccl_path",
     "ek_hip_bucketed_applicable", "ek_hip_bucketed_pair_create", "ek_hip_bucketed_pair_create_hinted", "ek_hip_bucketed_pair_create_masked", "ek_hip_bucketed_pair_create_scalar", "ek_hip_bucketed_pair_create_scalar_device", "ek_hip_bucketed_addend_adjoint", "ek_hip_bucketed_reduce", "ek_hip_bucketed_scatter_add", "ek_hip_bucketed_scatter_add_scaled", "ek_hip_bucketed_early_pair",
     "ek_hip_bucketed_piece_counts", "ek_hip_bucketed_destroy", "ek_hip_bucketed_partition_retain", "ek_hip_bucket_partition_release", "ek_hip_bucketed_pair_create_on", "ek_hip_index_partition_create", "ek_hip_index_partition_get", "ek_hip_index_partition_destroy", "ek_hip_gather_address",
+    "ek_hip_search_sorted", "ek_hip_search_sorted_plan",
 ]
 
 
@@ -494,6 +495,21 @@ def psum(a):
     out = Buf(a.dtype, a.n)
     check(lib.ek_hip_psum(a.ek, ctypes.c_void_p(out.ptr), ctypes.c_void_p(a.ptr), ctypes.c_size_t(a.n)))
     return out
+
+
+def search_sorted(table, needles, right=False):
+    """per needle the number of table entries before it (right: not after it), uint32 (ek_hip_search_sorted)"""
+    out = Buf(np.uint32, needles.n)
+    check(lib.ek_hip_search_sorted(table.ek, ctypes.c_void_p(out.ptr), ctypes.c_void_p(table.ptr if table.n else None),
+                                   ctypes.c_size_t(table.n), ctypes.c_void_p(needles.ptr), ctypes.c_size_t(needles.n), int(bool(right))))
+    return out
+
+
+def search_sorted_plan(dtype, K):
+    """(resident, stride, global_steps): what ek_hip_search_sorted does for a table of K entries of `dtype` (host only)"""
+    r, s, g = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(lib.ek_hip_search_sorted_plan(NP2EK[np.dtype(dtype)], ctypes.c_size_t(K), ctypes.byref(r), ctypes.byref(s), ctypes.byref(g)))
+    return r.value, s.value, g.value
 
 
 class Bucketed:

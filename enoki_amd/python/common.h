@@ -241,6 +241,10 @@ template <typename Array> py::class_<Array> bind_array(py::module_ &m, const cha
         if constexpr (!IsDiff)
             m.def("compress", [](const Array &a, const Mask &mk) { return compress(a, mk); });
         m.def("reverse", [](const Array &a) { return reverse(a); });
+        // per needle the number of entries of a sorted table before it (right: not after it), as UInt32: the binary_search
+        // loop over gather(table, min(i, K - 1)) < needles in one kernel
+        m.def("search_sorted", [](const Array &table, const Array &needles, bool right) { return search_sorted(table, needles, right); },
+              "table"_a, "needles"_a, "right"_a = false);
     }
 
     if constexpr (IsFloat) {
@@ -348,6 +352,8 @@ template <typename Array> py::class_<Array> bind_array(py::module_ &m, const cha
         m.def("mulhi", [](const Array &a, const Array &b) { return mulhi(a, b); });
         // floor(log2(a)) = (bits - 1) - lzcnt(a)  (array_router.h log2i, bound in src/python/common.h:832)
         m.def("log2i", [](const Array &a) { return log2i(a); });
+        if constexpr (IsDiff)     // always false: an index array (the result of search_sorted, say) carries no gradient
+            m.def("requires_gradient", [](const Array &a) { return requires_gradient(a); });
         if constexpr (std::is_same_v<Scalar, uint32_t>)
             // every lane searches [start, end) for the first index where pred(index) is False (cuda_1d.cpp:85-92,
             // cuda_autodiff_1d.cpp; array_utils.h:130-171): pred maps a UInt32 array to a Mask

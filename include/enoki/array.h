@@ -1632,6 +1632,17 @@ inline Index binary_search(scalar_t<Index> start_, scalar_t<Index> end_, const P
     return binary_search<Index, Predicate>(start_, end_, pred);
 }
 
+/// Lower bound (`right`: upper bound) of every needle in a sorted table: the number of entries t with t < needle (t <= needle).
+/// What binary_search(0, K, [&](Index i) { return gather<T>(table, min(i, K - 1)) < needles; }) returns, in one kernel.
+template <typename Table, typename Needles, typename Index = uint32_array_t<Table>>
+inline Index search_sorted(const Table &table, const Needles &needles, bool right = false) {
+    static_assert(array_depth_v<Table> == 1, "search_sorted(): the table is a flat array");
+    static_assert(std::is_same_v<Table, Needles> || std::is_same_v<Needles, scalar_t<Table>>,
+                  "search_sorted(): table and needles must have the same element type");
+    if constexpr (std::is_same_v<Table, Needles>) return Index(table.search_sorted_(needles, right));
+    else return Index(table.search_sorted_(Table(needles), right));
+}
+
 /// Angle between two unit vectors / between a unit vector and the z axis, well behaved near 0 and pi (array_math.h:1404-1436)
 template <typename T> inline auto unit_angle(const T &a, const T &b) {
     auto dot_uv = dot(a, b);

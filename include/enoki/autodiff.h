@@ -761,6 +761,11 @@ template <typename Type_> struct DiffArray : ArrayTag {
         return create(idx, reverse(m_value));
     }
 
+    /// A position in a sorted table is piecewise constant in table and needles: searched on the detached values, no node, no edges
+    ReplaceScalar<uint32_t> search_sorted_(const DiffArray &needles, bool right) const {
+        return ReplaceScalar<uint32_t>(m_value.search_sorted_(needles.m_value, right));
+    }
+
     // -----------------------------------------------------------------------------------------
     //  Initializers (forwarded), storage access
     // -----------------------------------------------------------------------------------------

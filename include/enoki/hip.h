@@ -1737,6 +1737,21 @@ template <typename Value_> struct HIPArray : ArrayTag {
         return r;
     }
 
+    /// Per needle the number of entries of this sorted array before it (`right`: not after it) in one launch
+    /// (ek_hip_search_sorted); a host-scalar needle is searched as an array of one entry
+    HIPArray<uint32_t> search_sorted_(const HIPArray &needles, bool right) const {
+        static_assert(!IsMask, "search_sorted_(): not defined for masks");
+        const size_t n = needles.size();
+        if (n == 0) return HIPArray<uint32_t>();
+        needles.materialize();
+        HIPArray<uint32_t> r = HIPArray<uint32_t>::empty_(n);
+        const size_t k = size();
+        if (k) materialize();
+        detail::hip_check(ek_hip_search_sorted(Type, (uint32_t *) r.m_buf->ptr, k ? ptr_() : nullptr, k, needles.ptr_(), n, right ? 1 : 0),
+                          "search_sorted_");
+        return r;
+    }
+
     // -----------------------------------------------------------------------------------------
     //  Storage access
     // -----------------------------------------------------------------------------------------

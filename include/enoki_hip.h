@@ -544,6 +544,18 @@ EK_API int ek_hip_hsum_safe_mul(int type, void *out, const ek_operand *w, const 
 EK_API int ek_hip_mask_reduce(int op, const uint8_t *mask, size_t n, uint64_t *host_result);
 /* inclusive prefix sum (cuda.h:717-726 / horiz.cu:182-200) */
 EK_API int ek_hip_psum(int type, void *out, const void *in, size_t n);
+/* Lower / upper bound in a sorted table: out[i] = the number of entries t of table[0 .. K) with t < needles[i] (right != 0:
+ * t <= needles[i]) -- inverting a CDF, finding a spline interval, sampling a discrete distribution.  What
+ * binary_search(0, K, [&](i) { return gather(T, min(i, K - 1)) < v; }) (array_utils.h:130-171) returns, bit for bit, in ONE launch
+ * instead of log2(K) + 1 rounds of four vertical ops.  I32 .. F64 (EK_BOOL: EK_ERR_UNSUPPORTED); the comparisons are the type's own:
+ * unsigned for U32 / U64, -0.0 < 0.0 false, denormals not flushed, a NaN needle compares false everywhere and yields 0 on both
+ * sides (numpy.searchsorted answers K).  The table is sorted ascending and holds no NaN; otherwise the result is unspecified, but
+ * the call stays in bounds and terminates.  K = 0: zeros.  K >= 2^32: EK_ERR_UNSUPPORTED.  No host wait: capturable.
+ * Tables of up to 64 KiB are searched in LDS; of a larger one every stride-th entry is, and the last log2(stride) steps of a
+ * search read a window of `stride` consecutive entries in global memory.  ek_hip_search_sorted_plan (host only) reports that
+ * split for a type and K: *resident entries or samples in LDS, *stride (1: resident whole), *global_steps per needle. */
+EK_API int ek_hip_search_sorted(int type, uint32_t *out, const void *table, size_t K, const void *needles, size_t n, int right);
+EK_API int ek_hip_search_sorted_plan(int type, size_t K, int *resident, int *stride, int *global_steps);
 
 /* Stable sort of (key, element number) pairs by the low `key_bits` bits of 32-bit keys:
  *     keys_out = keys sorted ascending, perm_out[j] = original position of keys_out[j]; equal keys keep their order.
