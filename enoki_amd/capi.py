@@ -49,6 +49,7 @@ EXPORTS = [
     "ek_hip_bucketed_applicable", "ek_hip_bucketed_pair_create", "ek_hip_bucketed_pair_create_hinted", "ek_hip_bucketed_pair_create_masked", "ek_hip_bucketed_pair_create_scalar", "ek_hip_bucketed_pair_create_scalar_device", "ek_hip_bucketed_addend_adjoint", "ek_hip_bucketed_reduce", "ek_hip_bucketed_scatter_add", "ek_hip_bucketed_scatter_add_scaled", "ek_hip_bucketed_early_pair",
     "ek_hip_bucketed_piece_counts", "ek_hip_bucketed_destroy", "ek_hip_bucketed_partition_retain", "ek_hip_bucket_partition_release", "ek_hip_bucketed_pair_create_on", "ek_hip_index_partition_create", "ek_hip_index_partition_get", "ek_hip_index_partition_destroy", "ek_hip_gather_address",
     "ek_hip_search_sorted", "ek_hip_search_sorted_plan",
+    "ek_hip_reduce_blocks", "ek_hip_reduce_blocks_plan", "ek_hip_repeat",
 ]
 
 
@@ -510,6 +511,34 @@ def search_sorted_plan(dtype, K):
     r, s, g = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     check(lib.ek_hip_search_sorted_plan(NP2EK[np.dtype(dtype)], ctypes.c_size_t(K), ctypes.byref(r), ctypes.byref(s), ctypes.byref(g)))
     return r.value, s.value, g.value
+
+
+def reduce_blocks(op, a, block):
+    """out[j] = op over a[j * block : (j + 1) * block] for the a.n / block blocks of `block` entries (ek_hip_reduce_blocks)"""
+    block = int(block)
+    out = Buf(a.dtype, a.n // block if block else 0)
+    check(lib.ek_hip_reduce_blocks(REDUCE[op], a.ek, ctypes.c_void_p(out.ptr), ctypes.c_void_p(a.ptr if a.n else None),
+                                   ctypes.c_size_t(a.n), ctypes.c_size_t(block)))
+    return out
+
+
+def repeat(a, block, out=None):
+    """out[i] = a[i // block], numpy.repeat(a, block) (ek_hip_repeat); `out`: write into this array of a.n * block entries"""
+    block = int(block)
+    if out is None:
+        out = Buf(a.dtype, a.n * block)
+    check(lib.ek_hip_repeat(a.ek, ctypes.c_void_p(out.ptr), ctypes.c_void_p(a.ptr if a.n else None), ctypes.c_size_t(a.n),
+                            ctypes.c_size_t(block)))
+    return out
+
+
+def reduce_blocks_plan(dtype, n, block, compute_units=0):
+    """(regime, splits, workgroups): the route ek_hip_reduce_blocks takes for n entries of `dtype` in blocks of `block` (host only).
+    regime: 0 copy, 1 whole-array reduction, 2 packed, 3 one workgroup per block, 4 split into `splits` pieces per block"""
+    r, s, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
+    check(lib.ek_hip_reduce_blocks_plan(NP2EK[np.dtype(dtype)], ctypes.c_size_t(n), ctypes.c_size_t(block), int(compute_units),
+                                        ctypes.byref(r), ctypes.byref(s), ctypes.byref(w)))
+    return r.value, s.value, w.value
 
 
 class Bucketed:

@@ -1,0 +1,323 @@
+// Block reductions: out[j] = reduce(in[j * B .. (j + 1) * B)) for the n / B blocks of B consecutive entries (the spp samples of a
+// pixel, a row of a row-major matrix), and their transpose  repeat: out[i] = in[i / B].
+//
+// The spellings these replace, scatter_add(zero(n / B), x, arange(n) / B) and gather(v, arange(n) / B), stream an n-entry index
+// array that carries no information.  The algorithmic traffic is one pass: sizeof(T) * (1 + 1 / B) bytes per element, both ways.
+//
+// ek_hip_reduce_blocks takes one of five routes, chosen by block_plan() (what ek_hip_reduce_blocks_plan reports):
+//   0 copy    B == 1.
+//   1 whole   B == n: ek_hip_reduce, bit for bit.
+//   2 packed  B <= 1024.  A workgroup takes a tile of whole blocks, at most 16 KiB and a multiple of the vector width in blocks, so
+//             every tile starts at the base pointer's alignment.  The tile goes to LDS with 16-byte non-temporal loads (the few
+//             elements in front of the first 16-byte boundary and behind the last one by element, and the tile is shifted in LDS by
+//             that many so that the LDS stores are 16-byte stores too): a misaligned view costs no more than an aligned one, and the
+//             result does not depend on the alignment.  Then every block gets a group of G = 2^ceil(log2(min(B, 64))) ADJACENT lanes:
+//             lane l of the group combines entries l, l + G, .. of its block and the group finishes with log2(G) shuffle steps.
+//             Groups, not padding: the lanes of a wave then read (64 / G) * min(B, G) <= 64 consecutive LDS words per access -- no
+//             two in one bank for any B, where one lane per block at stride B is gcd(B, 64)-way conflicted and padding would have to
+//             change with B -- and a block of 64 entries is 1 read and 6 shuffles per lane instead of 64 dependent reads in one lane.
+//   3 one workgroup per block, B > 1024: the block is streamed as k_reduce_stage1 streams an array (16-byte non-temporal loads, four
+//             in flight per lane, four accumulators, the 256-thread fold); the entries in front of the block's first 16-byte boundary
+//             and behind its last are taken one per lane, so B * sizeof(T) need not be a multiple of 16 and neither need the base.
+//   4 split   fewer than 2 x #CU blocks of at least 16 Ki entries: every block is cut into S pieces of P entries (P a multiple of the
+//             vector width: the pieces of a block share its alignment) so that about 4 x #CU workgroups run; the same kernel as 3
+//             writes m x S partials, which the packed kernel folds with B = S.  Two launches in a fixed order.
+// No atomics, no read-back, no host wait; the partials of 4 come from the caching allocator (capturable).  Every sum has a fixed
+// shape for a given (type, op, n, B, alignment, #CU): run-to-run identical.
+#include "ek_reduce.h"
+
+#include <algorithm>
+
+namespace ek {
+
+constexpr size_t kPackedTileBytes = 16 * 1024;
+constexpr size_t kPackedMaxBlock = 1024;          // entries: at least one vector width of blocks per tile for 4- and 8-byte types
+constexpr size_t kSplitMinPiece = 8192;           // entries
+constexpr size_t kSplitMaxPieces = kPackedMaxBlock;
+constexpr size_t kMaxGrid = 0x7FFFFFFFull;
+
+struct BlockPlan {
+    int regime;
+    size_t splits, piece;          // 4: pieces per block and entries per piece (the last piece of a block may be shorter)
+    uint32_t tile_blocks, glog;    // 2: blocks per tile, log2(lanes per block)
+    size_t workgroups;             // grid of the first launch
+};
+
+static void packed_shape(size_t elem, size_t m, size_t B, BlockPlan &p) {
+    const size_t N = 16 / elem, E = kPackedTileBytes / elem;
+    p.tile_blocks = (uint32_t) std::max<size_t>(N, E / B / N * N);
+    p.glog = 0;
+    while ((1u << p.glog) < B && p.glog < 6) p.glog++;
+    p.workgroups = std::min<size_t>((m + p.tile_blocks - 1) / p.tile_blocks, kMaxGrid);
+}
+
+static BlockPlan block_plan(size_t elem, size_t n, size_t B, int num_cu) {
+    BlockPlan p = { 0, 1, B, 0, 0, 1 };
+    const size_t m = n / B, N = 16 / elem, cu = num_cu > 0 ? (size_t) num_cu : 256;
+    if (B == 1) return p;
+    if (B == n) {
+        // (the grid of ek_hip_reduce at its default tuning)
+        p.regime = 1;
+        p.workgroups = std::min<size_t>(std::min<size_t>((((n / N + 3) / 4 + 1) + 255) / 256, cu * 4), 2048);
+        return p;
+    }
+    if (B <= kPackedMaxBlock) {
+        p.regime = 2;
+        packed_shape(elem, m, B, p);
+        return p;
+    }
+    p.regime = 3;
+    if (m < 2 * cu) {
+        size_t S = std::min(std::min((4 * cu + m - 1) / m, B / kSplitMinPiece), kSplitMaxPieces);
+        if (S >= 2) {
+            p.piece = ((B + S - 1) / S + N - 1) / N * N;
+            p.splits = (B + p.piece - 1) / p.piece;        // (every piece holds at least one entry)
+            if (p.splits >= 2) p.regime = 4;
+            else { p.splits = 1; p.piece = B; }
+        }
+    }
+    p.workgroups = std::min<size_t>(m * p.splits, kMaxGrid);
+    return p;
+}
+
+/// entries of `p` in front of its first 16-byte boundary (p is a multiple of sizeof(T))
+template <typename T> __device__ __forceinline__ uint32_t head_of(const T *p) {
+    return (uint32_t) (((16u - (uint32_t) (reinterpret_cast<uintptr_t>(p) & 15u)) & 15u) / sizeof(T));
+}
+
+template <typename R, typename T>
+__global__ __launch_bounds__(256) void k_reduce_packed(T *__restrict__ out, const T *__restrict__ in, size_t m, uint32_t B, uint32_t tile_blocks,
+                                                       uint32_t glog, size_t tiles) {
+    constexpr uint32_t N = 16 / sizeof(T), E = kPackedTileBytes / sizeof(T);
+    __shared__ __attribute__((aligned(16))) T tile[E + N];
+    const uint32_t G = 1u << glog, group = threadIdx.x >> glog, l = threadIdx.x & (G - 1), groups = 256u >> glog;
+    for (size_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const size_t b0 = t * tile_blocks;
+        const uint32_t nb = (uint32_t) (m - b0 < tile_blocks ? m - b0 : tile_blocks), len = nb * B;       // len <= E
+        const T *src = in + b0 * B;
+        uint32_t head = head_of(src);
+        if (head > len) head = len;
+        // element e of the tile lives at tile[shift + e]: the first whole vector lands on a 16-byte boundary of LDS
+        const uint32_t shift = (N - head) % N, nvec = (len - head) / N, tail = len - head - nvec * N;
+        T *dst = tile + shift;
+        if (threadIdx.x < head) dst[threadIdx.x] = src[threadIdx.x];
+#pragma unroll 4
+        for (uint32_t v = threadIdx.x; v < nvec; v += 256)
+            *reinterpret_cast<Pack<T, N> *>(dst + head + v * N) = pack_load<T, N, true>(src + head + v * N);
+        if (threadIdx.x < tail) dst[head + nvec * N + threadIdx.x] = src[head + nvec * N + threadIdx.x];
+        __syncthreads();
+        // (the same trip count for every lane: the shuffles below are executed by whole waves)
+        const uint32_t trips = (nb + groups - 1) / groups;
+        for (uint32_t it = 0; it < trips; ++it) {
+            const uint32_t blk = it * groups + group;
+            T acc = R::identity();
+            if (blk < nb) {
+                const T *b = dst + blk * B;
+                for (uint32_t k = l; k < B; k += G) acc = R::combine(acc, b[k]);
+            }
+            for (uint32_t d = G >> 1; d; d >>= 1) acc = R::combine(acc, shfl_down(acc, (int) d));
+            if (l == 0 && blk < nb) out[b0 + blk] = acc;
+        }
+        __syncthreads();
+    }
+}
+
+/// segment = piece s of block j (S pieces of `piece` entries per block; S == 1: the whole block), one workgroup each
+template <typename R, typename T>
+__global__ __launch_bounds__(256) void k_reduce_segments(T *__restrict__ out, const T *__restrict__ in, size_t B, size_t piece, uint32_t S,
+                                                         size_t segments) {
+    constexpr uint32_t N = 16 / sizeof(T), U = 4;
+    for (size_t seg = blockIdx.x; seg < segments; seg += gridDim.x) {
+        size_t j = seg, off = 0;
+        if (S > 1) { j = seg / S; off = (seg - j * S) * piece; }
+        const size_t len = B - off < piece ? B - off : piece;
+        const T *src = in + j * B + off;
+        size_t head = head_of(src);
+        if (head > len) head = len;
+        const size_t nvec = (len - head) / N, tail = len - head - nvec * N;
+        const T *vsrc = src + head;
+        T acc[U];
+#pragma unroll
+        for (uint32_t k = 0; k < U; ++k) acc[k] = R::identity();
+        for (size_t v0 = threadIdx.x; v0 < nvec; v0 += 256 * U) {
+            Pack<T, N> p[U];
+#pragma unroll
+            for (uint32_t k = 0; k < U; ++k)
+                if (v0 + k * 256 < nvec) p[k] = pack_load<T, N, true>(vsrc + (v0 + k * 256) * N);
+#pragma unroll
+            for (uint32_t k = 0; k < U; ++k) {
+                if (v0 + k * 256 < nvec) {
+#pragma unroll
+                    for (uint32_t i = 0; i < N; ++i) acc[k] = R::combine(acc[k], p[k].v[i]);
+                }
+            }
+        }
+        if (threadIdx.x < head) acc[0] = R::combine(acc[0], src[threadIdx.x]);
+        if (threadIdx.x < tail) acc[1] = R::combine(acc[1], vsrc[nvec * N + threadIdx.x]);
+        T v = R::combine(R::combine(acc[0], acc[1]), R::combine(acc[2], acc[3]));
+        v = block_reduce<R>(v);
+        if (threadIdx.x == 0) out[seg] = v;
+        __syncthreads();                                  // (block_reduce's LDS words are written again by the next segment)
+    }
+}
+
+template <typename R, typename T> static int launch_packed(const char *name, T *out, const T *in, size_t m, size_t B, const BlockPlan &p) {
+    const size_t tiles = (m + p.tile_blocks - 1) / p.tile_blocks;
+    hipLaunchKernelGGL((k_reduce_packed<R, T>), dim3((unsigned) p.workgroups), dim3(256), 0, ctx().stream, out, in, m, (uint32_t) B, p.tile_blocks,
+                       p.glog, tiles);
+    EK_LAUNCH_CHECK(name, m * B, (m * B + m) * sizeof(T));
+    return EK_OK;
+}
+
+template <int Op, typename T> static int reduce_blocks_op(T *out, const T *in, size_t n, size_t B, const BlockPlan &p) {
+    using R = Reducer<Op, T>;
+    RoctxRange range("enoki-hip: block reduction");
+    Context &c = ctx();
+    const size_t m = n / B;
+    if (p.regime == 2) return launch_packed<R, T>("reduce_blocks_packed", out, in, m, B, p);
+    if (p.regime == 3) {
+        hipLaunchKernelGGL((k_reduce_segments<R, T>), dim3((unsigned) p.workgroups), dim3(256), 0, c.stream, out, in, B, B, 1u, m);
+        EK_LAUNCH_CHECK("reduce_blocks", n, (n + m) * sizeof(T));
+        return EK_OK;
+    }
+    const size_t segments = m * p.splits;
+    void *partials = nullptr;
+    if (int rc = ek_hip_malloc(segments * sizeof(T), &partials)) return rc;
+    BlockPlan fold = p;
+    packed_shape(sizeof(T), m, p.splits, fold);
+    hipLaunchKernelGGL((k_reduce_segments<R, T>), dim3((unsigned) p.workgroups), dim3(256), 0, c.stream, (T *) partials, in, B, p.piece,
+                       (uint32_t) p.splits, segments);
+    int rc = EK_OK;
+    if (hipError_t err = hipGetLastError(); err != hipSuccess) rc = hip_fail(err, "reduce_blocks_split", __FILE__, __LINE__);
+    else {
+        note_launch("reduce_blocks_split", n, (n + segments) * sizeof(T));
+        rc = launch_packed<R, T>("reduce_blocks_fold", out, (const T *) partials, m, p.splits, fold);
+    }
+    ek_hip_free(partials);   // stream-ordered reuse
+    return rc;
+}
+
+template <typename T> static int reduce_blocks_typed(int op, void *out, const void *in, size_t n, size_t B, const BlockPlan &p) {
+    switch (op) {
+        case EK_HSUM: return reduce_blocks_op<EK_HSUM, T>((T *) out, (const T *) in, n, B, p);
+        case EK_HPROD: return reduce_blocks_op<EK_HPROD, T>((T *) out, (const T *) in, n, B, p);
+        case EK_HMIN: return reduce_blocks_op<EK_HMIN, T>((T *) out, (const T *) in, n, B, p);
+        default: return reduce_blocks_op<EK_HMAX, T>((T *) out, (const T *) in, n, B, p);
+    }
+}
+
+// ---- repeat --------------------------------------------------------------------------------------------------------------
+// One 16-byte non-temporal store per lane and trip.  A lane divides ONCE (its first element / B); every later trip is `threads`
+// vectors further on: quotient and remainder advance by the host's (dq, dr) with one conditional carry.  Inside a vector the
+// remainder counts up to B.  The host peels the elements in front of the first 16-byte boundary of `out`; they and the elements
+// behind the last whole vector (at most 6 together) are written one per lane by workgroup 0.
+template <typename T>
+__global__ __launch_bounds__(256) void k_repeat(T *__restrict__ out, const T *__restrict__ in, size_t total, size_t B, uint32_t peel, size_t dq, size_t dr) {
+    constexpr uint32_t N = 16 / sizeof(T);
+    const size_t items = (total - peel) / N, threads = (size_t) gridDim.x * 256;
+    size_t item = (size_t) blockIdx.x * 256 + threadIdx.x;
+    if (item < items) {
+        const size_t e = peel + item * N;
+        size_t q = e / B, r = e - q * B;
+        for (; item < items; item += threads) {
+            Pack<T, N> p;
+            size_t qq = q, rr = r;
+#pragma unroll
+            for (uint32_t i = 0; i < N; ++i) {
+                p.v[i] = in[qq];
+                if (++rr == B) { rr = 0; ++qq; }
+            }
+            pack_store<T, N, true>(out + peel + item * N, p);
+            q += dq;
+            r += dr;
+            if (r >= B) { r -= B; ++q; }
+        }
+    }
+    const uint32_t rest = peel + (uint32_t) ((total - peel) - items * N);
+    if (blockIdx.x == 0 && threadIdx.x < rest) {
+        const size_t e = threadIdx.x < peel ? threadIdx.x : peel + items * N + (threadIdx.x - peel);
+        out[e] = in[e / B];
+    }
+}
+
+template <typename T> static int repeat_typed(void *out, const void *in, size_t m, size_t B) {
+    Context &c = ctx();
+    constexpr size_t N = 16 / sizeof(T);
+    const size_t total = m * B;
+    size_t peel = ((16 - (reinterpret_cast<uintptr_t>(out) & 15u)) & 15u) / sizeof(T);
+    if (peel > total) peel = total;
+    const size_t items = (total - peel) / N;
+    size_t blocks = (items + 255) / 256, cap = (size_t) c.num_cu * 16;
+    if (blocks > cap) blocks = cap;
+    if (blocks == 0) blocks = 1;
+    const size_t step = blocks * 256 * N;
+    hipLaunchKernelGGL((k_repeat<T>), dim3((unsigned) blocks), dim3(256), 0, c.stream, (T *) out, (const T *) in, total, B, (uint32_t) peel,
+                       step / B, step % B);
+    EK_LAUNCH_CHECK("repeat", total, (total + m) * sizeof(T));
+    return EK_OK;
+}
+
+static int block_type_check(const char *what, int type) {
+    switch (type) {
+        case EK_I32: case EK_U32: case EK_I64: case EK_U64: case EK_F32: case EK_F64: return EK_OK;
+        default: return fail(EK_ERR_UNSUPPORTED, "%s: unsupported type %d", what, type);
+    }
+}
+
+} // namespace ek
+
+using namespace ek;
+
+extern "C" {
+
+int ek_hip_reduce_blocks_plan(int type, size_t n, size_t block, int compute_units, int *regime, int *splits, size_t *workgroups) {
+    if (int rc = block_type_check("ek_hip_reduce_blocks_plan()", type)) return rc;
+    if (block == 0 || n % block != 0)
+        return fail(EK_ERR_INVALID, "ek_hip_reduce_blocks_plan(): %zu entries are no whole number of blocks of %zu", n, block);
+    if (compute_units < 0) return fail(EK_ERR_INVALID, "ek_hip_reduce_blocks_plan(): %d compute units", compute_units);
+    BlockPlan p = { 0, 1, block, 0, 0, 0 };
+    if (n) p = block_plan(type_size(type), n, block, compute_units);
+    if (regime) *regime = p.regime;
+    if (splits) *splits = (int) p.splits;
+    if (workgroups) *workgroups = p.workgroups;
+    return EK_OK;
+}
+
+int ek_hip_reduce_blocks(int op, int type, void *out, const void *in, size_t n, size_t block) {
+    if (int rc = ensure_init()) return rc;
+    if (op < 0 || op >= EK_REDUCE_COUNT) return fail(EK_ERR_INVALID, "ek_hip_reduce_blocks(): unknown op %d", op);
+    if (int rc = block_type_check("ek_hip_reduce_blocks()", type)) return rc;
+    if (block == 0 || n % block != 0)
+        return fail(EK_ERR_INVALID, "ek_hip_reduce_blocks(): %zu entries are no whole number of blocks of %zu", n, block);
+    if (n == 0) return EK_OK;
+    const size_t elem = type_size(type);
+    if (!out || !in) return fail(EK_ERR_INVALID, "ek_hip_reduce_blocks(): null pointer");
+    if ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(in)) & (elem - 1))
+        return fail(EK_ERR_INVALID, "ek_hip_reduce_blocks(): pointer not aligned to the element size");
+    const BlockPlan p = block_plan(elem, n, block, ctx().num_cu);
+    if (p.regime == 0) return ek_hip_memcpy_device(out, in, n * elem);
+    if (p.regime == 1) return ek_hip_reduce(op, type, out, in, n);
+    switch (type) {
+        case EK_I32: return reduce_blocks_typed<int32_t>(op, out, in, n, block, p);
+        case EK_U32: return reduce_blocks_typed<uint32_t>(op, out, in, n, block, p);
+        case EK_I64: return reduce_blocks_typed<int64_t>(op, out, in, n, block, p);
+        case EK_U64: return reduce_blocks_typed<uint64_t>(op, out, in, n, block, p);
+        case EK_F32: return reduce_blocks_typed<float>(op, out, in, n, block, p);
+        default: return reduce_blocks_typed<double>(op, out, in, n, block, p);
+    }
+}
+
+int ek_hip_repeat(int type, void *out, const void *in, size_t m, size_t block) {
+    if (int rc = ensure_init()) return rc;
+    if (int rc = block_type_check("ek_hip_repeat()", type)) return rc;
+    if (block == 0) return fail(EK_ERR_INVALID, "ek_hip_repeat(): blocks of 0 entries");
+    if (m == 0) return EK_OK;
+    const size_t elem = type_size(type);
+    if (!out || !in) return fail(EK_ERR_INVALID, "ek_hip_repeat(): null pointer");
+    if ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(in)) & (elem - 1))
+        return fail(EK_ERR_INVALID, "ek_hip_repeat(): pointer not aligned to the element size");
+    if (block == 1) return ek_hip_memcpy_device(out, in, m * elem);
+    return elem == 4 ? repeat_typed<uint32_t>(out, in, m, block) : repeat_typed<uint64_t>(out, in, m, block);
+}
+
+}

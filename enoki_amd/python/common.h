@@ -245,6 +245,13 @@ template <typename Array> py::class_<Array> bind_array(py::module_ &m, const cha
         // loop over gather(table, min(i, K - 1)) < needles in one kernel
         m.def("search_sorted", [](const Array &table, const Array &needles, bool right) { return search_sorted(table, needles, right); },
               "table"_a, "needles"_a, "right"_a = false);
+        // one value per block of `block` consecutive entries (len(array) a multiple of block), and the transpose: every entry
+        // `block` times in a row (numpy.repeat); block_sum and repeat are differentiable
+        m.def("block_sum", [](const Array &a, size_t block) { return block_sum(a, block); }, "array"_a, "block"_a);
+        m.def("block_prod", [](const Array &a, size_t block) { return block_prod(a, block); }, "array"_a, "block"_a);
+        m.def("block_min", [](const Array &a, size_t block) { return block_min(a, block); }, "array"_a, "block"_a);
+        m.def("block_max", [](const Array &a, size_t block) { return block_max(a, block); }, "array"_a, "block"_a);
+        m.def("repeat", [](const Array &a, size_t block) { return repeat(a, block); }, "array"_a, "block"_a);
     }
 
     if constexpr (IsFloat) {

@@ -524,6 +524,48 @@ template <typename Value> auto Tape<Value>::append_psum(Index source) -> Index {
     return target;
 }
 
+// block_sum and repeat are each other's transpose, so one Special serves both nodes: `sums` says that the node is the block sum of
+// its source (forward reduces the source's gradient, backward repeats the node's); otherwise the node repeats its source and the
+// directions swap.  A size-1 gradient is a broadcast seed (forward(x), backward of an hsum): widened to its node's size first.
+namespace detail {
+    template <typename TapeT, typename Value> struct BlockTranspose : TapeT::Special {
+        size_t block;
+        bool sums;
+        BlockTranspose(size_t block, bool sums) : block(block), sums(sums) { }
+        Value apply(Value g, size_t size, bool reduce) const {
+            if (g.size() == 1 && size != 1) set_slices(g, size);
+            return reduce ? block_sum(g, block) : repeat(g, block);
+        }
+        void forward(typename TapeT::Detail *detail, typename TapeT::Index target, const typename TapeT::Edge &edge) const override {
+            auto &s = detail->node(edge.source);
+            TapeT::Detail::accumulate(detail->node(target).grad, apply(s.grad, s.size, sums));
+        }
+        void backward(typename TapeT::Detail *detail, typename TapeT::Index target, const typename TapeT::Edge &edge) const override {
+            auto &t = detail->node(target);
+            TapeT::Detail::accumulate(detail->node(edge.source).grad, apply(t.grad, t.size, !sums));
+        }
+    };
+}
+
+template <typename Value> auto Tape<Value>::append_block_sum(Index source, size_t block) -> Index {
+    if (source == 0) return 0;
+    const size_t size = d->node(source).size;
+    if (block == 0 || size % block != 0) throw std::runtime_error("Tape::append_block_sum(): the source is no whole number of blocks");
+    Index target = append_node(size / block, "block_sum");
+    d->node(target).edges.emplace_back(source, new detail::BlockTranspose<Tape, Value>(block, true));
+    inc_ref_int(source, target);
+    return target;
+}
+
+template <typename Value> auto Tape<Value>::append_repeat(Index source, size_t block) -> Index {
+    if (source == 0) return 0;
+    if (block == 0) throw std::runtime_error("Tape::append_repeat(): blocks of 0 entries");
+    Index target = append_node(d->node(source).size * block, "repeat");
+    d->node(target).edges.emplace_back(source, new detail::BlockTranspose<Tape, Value>(block, false));
+    inc_ref_int(source, target);
+    return target;
+}
+
 // ---------------------------------------------------------------------------------------------
 //  Reference counting (autodiff.cpp:681-774)
 // ---------------------------------------------------------------------------------------------

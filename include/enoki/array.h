@@ -1643,6 +1643,25 @@ inline Index search_sorted(const Table &table, const Needles &needles, bool righ
     else return Index(table.search_sorted_(Table(needles), right));
 }
 
+/// One value per block of `block` consecutive entries of a flat array (the spp samples of a pixel, a row of a row-major matrix):
+/// block_sum(x, B)[j] = x[j * B] + .. + x[(j + 1) * B - 1], likewise block_prod / block_min / block_max; size(x) is a multiple of B.
+/// repeat(x, B)[i] = x[i / B] is the transpose of block_sum (numpy.repeat).  One kernel each, no index array; block_sum and repeat
+/// are differentiable in both modes.  An array type without these members throws at run time.
+namespace detail {
+    template <typename T, typename = void> struct has_block_ops : std::false_type { };
+    template <typename T> struct has_block_ops<T, std::void_t<decltype(std::declval<const T &>().block_sum_(size_t(1))),
+                                                              decltype(std::declval<const T &>().repeat_(size_t(1)))>> : std::true_type { };
+}
+#define ENOKI_HIP_BLOCK_OP(name)                                                                                             \
+    template <typename T> inline T name(const T &x, size_t block) {                                                          \
+        static_assert(array_depth_v<T> == 1, #name "(): takes a flat array");                                               \
+        if constexpr (detail::has_block_ops<T>::value) return x.name##_(block);                                              \
+        else throw std::runtime_error(#name "(): not available for this array type");                                       \
+    }
+ENOKI_HIP_BLOCK_OP(block_sum) ENOKI_HIP_BLOCK_OP(block_prod) ENOKI_HIP_BLOCK_OP(block_min) ENOKI_HIP_BLOCK_OP(block_max)
+ENOKI_HIP_BLOCK_OP(repeat)
+#undef ENOKI_HIP_BLOCK_OP
+
 /// Angle between two unit vectors / between a unit vector and the z axis, well behaved near 0 and pi (array_math.h:1404-1436)
 template <typename T> inline auto unit_angle(const T &a, const T &b) {
     auto dot_uv = dot(a, b);

@@ -124,6 +124,10 @@ template <typename Type> struct Tape {
     /// enoki::vectorize-style -- enters the tape: examples/path_trace.cpp.)
     Index append_custom(Index source, size_t size, const char *label, std::function<Type(const Type &)> backward);
     Index append_reverse(Index source);
+    /// block_sum(source, block): one entry per block of `block` consecutive entries; its adjoint is repeat()
+    Index append_block_sum(Index source, size_t block);
+    /// repeat(source, block): every entry `block` times in a row; its adjoint is block_sum()
+    Index append_repeat(Index source, size_t block);
     void set_scatter_gather_operand(Index *index, size_t size, bool permute);
 
     // ---- reference counting (ext = held by DiffArray handles, int = held by graph edges) ----
@@ -759,6 +763,41 @@ template <typename Type_> struct DiffArray : ArrayTag {
             if (m_index) idx = tape()->append_reverse(m_index);
         }
         return create(idx, reverse(m_value));
+    }
+
+    /// Sum of every block of `block` consecutive entries / every entry `block` times in a row: each other's transpose, one tape
+    /// node each (Tape::append_block_sum / append_repeat)
+    DiffArray block_sum_(size_t block) const {
+        Type result = block_sum(m_value, block);
+        Index idx = 0;
+        if constexpr (Enabled) {
+            if (m_index) idx = tape()->append_block_sum(m_index, block);
+        }
+        return create(idx, std::move(result));
+    }
+
+    DiffArray repeat_(size_t block) const {
+        Type result = repeat(m_value, block);
+        Index idx = 0;
+        if constexpr (Enabled) {
+            if (m_index) idx = tape()->append_repeat(m_index, block);
+        }
+        return create(idx, std::move(result));
+    }
+
+    DiffArray block_prod_(size_t block) const {
+        if (Enabled && m_index != 0) throw std::runtime_error("DiffArray::block_prod_(): gradients not implemented");
+        return create(0, block_prod(m_value, block));
+    }
+
+    DiffArray block_min_(size_t block) const {
+        if (Enabled && m_index != 0) throw std::runtime_error("DiffArray::block_min_(): gradients not implemented");
+        return create(0, block_min(m_value, block));
+    }
+
+    DiffArray block_max_(size_t block) const {
+        if (Enabled && m_index != 0) throw std::runtime_error("DiffArray::block_max_(): gradients not implemented");
+        return create(0, block_max(m_value, block));
     }
 
     /// A position in a sorted table is piecewise constant in table and needles: searched on the detached values, no node, no edges

@@ -1752,6 +1752,41 @@ template <typename Value_> struct HIPArray : ArrayTag {
         return r;
     }
 
+    /// One value per block of `block` consecutive entries: out[j] = op over [j * block, (j + 1) * block) (ek_hip_reduce_blocks;
+    /// op: EK_HSUM .. EK_HMAX).  An unevaluated operand is evaluated once; a host scalar is an array of one entry.
+    HIPArray block_reduce_(int op, size_t block) const {
+        static_assert(!IsMask, "block_reduce_(): not defined for masks");
+        const size_t n = size();
+        if (block == 0 || n % block != 0)
+            throw std::runtime_error("HIPArray::block_reduce_(): " + std::to_string(n) + " entries are no whole number of blocks of " +
+                                     std::to_string(block));
+        if (!&ek_hip_reduce_blocks)
+            throw std::runtime_error("HIPArray::block_reduce_(): this C ABI has no entry ek_hip_reduce_blocks");
+        if (n == 0) return HIPArray();
+        materialize();
+        HIPArray r = empty_(n / block);
+        detail::hip_check(ek_hip_reduce_blocks(op, Type, r.m_buf->ptr, ptr_(), n, block), "block_reduce_");
+        return r;
+    }
+
+    HIPArray block_sum_(size_t block) const { return block_reduce_(EK_HSUM, block); }
+    HIPArray block_prod_(size_t block) const { return block_reduce_(EK_HPROD, block); }
+    HIPArray block_min_(size_t block) const { return block_reduce_(EK_HMIN, block); }
+    HIPArray block_max_(size_t block) const { return block_reduce_(EK_HMAX, block); }
+
+    /// Every entry `block` times in a row: out[i] = in[i / block] (ek_hip_repeat), the transpose of the block sum
+    HIPArray repeat_(size_t block) const {
+        static_assert(!IsMask, "repeat_(): not defined for masks");
+        if (block == 0) throw std::runtime_error("HIPArray::repeat_(): blocks of 0 entries");
+        if (!&ek_hip_repeat) throw std::runtime_error("HIPArray::repeat_(): this C ABI has no entry ek_hip_repeat");
+        const size_t m = size();
+        if (m == 0) return HIPArray();
+        materialize();
+        HIPArray r = empty_(m * block);
+        detail::hip_check(ek_hip_repeat(Type, r.m_buf->ptr, ptr_(), m, block), "repeat_");
+        return r;
+    }
+
     // -----------------------------------------------------------------------------------------
     //  Storage access
     // -----------------------------------------------------------------------------------------

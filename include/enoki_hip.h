@@ -556,6 +556,24 @@ EK_API int ek_hip_psum(int type, void *out, const void *in, size_t n);
  * split for a type and K: *resident entries or samples in LDS, *stride (1: resident whole), *global_steps per needle. */
 EK_API int ek_hip_search_sorted(int type, uint32_t *out, const void *table, size_t K, const void *needles, size_t n, int right);
 EK_API int ek_hip_search_sorted_plan(int type, size_t K, int *resident, int *stride, int *global_steps);
+/* Block reductions: out[j] = reduce_op(in[j * block .. (j + 1) * block)) for j < n / block -- the samples of a pixel summed into
+ * the image, the rows of a row-major matrix -- without the index array of scatter_add(zero(n / block), x, arange(n) / block).
+ * op: EK_HSUM / EK_HPROD / EK_HMIN / EK_HMAX with the semantics of ek_hip_reduce (integer sums and products wrap; floating point
+ * hmin / hmax are minNum / maxNum: a NaN is ignored unless the whole block is NaN, -0 < +0); I32 .. F64.  block == 0 or
+ * n % block != 0: EK_ERR_INVALID; n == 0: nothing is launched; block == 1 is a device copy; block == n IS ek_hip_reduce (bit
+ * for bit).  The pointers need only element alignment.  No atomics, no read-back, no host wait (capturable); the result is
+ * bit-identical from run to run for a given (type, op, n, block, pointer alignment, device).
+ * ek_hip_reduce_blocks_plan (host only, no device access; compute_units == 0: 256) reports the route ek_hip_reduce_blocks takes:
+ * *regime 0 copy, 1 whole-array reduction, 2 packed (a workgroup stages a tile of whole blocks in LDS, a power-of-two group of
+ * adjacent lanes per block), 3 one workgroup per block, 4 split (few large blocks: *splits >= 2 pieces per block and a packed
+ * fold of the partials; *splits == 1 otherwise), and *workgroups, the grid of its first launch.
+ * EK_OPTIONAL: enoki/hip.h asks for the entries' addresses first and throws without them. */
+EK_API EK_OPTIONAL int ek_hip_reduce_blocks(int op, int type, void *out, const void *in, size_t n, size_t block);
+EK_API EK_OPTIONAL int ek_hip_reduce_blocks_plan(int type, size_t n, size_t block, int compute_units, int *regime, int *splits, size_t *workgroups);
+/* The transpose of the block sum (numpy.repeat): out[i] = in[i / block] for i < m * block, without the index array of
+ * gather(v, arange(m * block) / block).  Keyed on the element size: I32 .. F64.  block == 0: EK_ERR_INVALID; m == 0: nothing is
+ * launched; block == 1 is a device copy.  16-byte stores wherever `out` allows; one division per lane.  EK_OPTIONAL as above. */
+EK_API EK_OPTIONAL int ek_hip_repeat(int type, void *out, const void *in, size_t m, size_t block);
 
 /* Stable sort of (key, element number) pairs by the low `key_bits` bits of 32-bit keys:
  *     keys_out = keys sorted ascending, perm_out[j] = original position of keys_out[j]; equal keys keep their order.
