@@ -50,6 +50,7 @@ EXPORTS = [
     "ek_hip_bucketed_piece_counts", "ek_hip_bucketed_destroy", "ek_hip_bucketed_partition_retain", "ek_hip_bucket_partition_release", "ek_hip_bucketed_pair_create_on", "ek_hip_index_partition_create", "ek_hip_index_partition_get", "ek_hip_index_partition_destroy", "ek_hip_gather_address",
     "ek_hip_search_sorted", "ek_hip_search_sorted_plan",
     "ek_hip_reduce_blocks", "ek_hip_reduce_blocks_plan", "ek_hip_repeat",
+    "ek_hip_psum_blocks", "ek_hip_psum_blocks_plan",
 ]
 
 
@@ -538,6 +539,29 @@ def reduce_blocks_plan(dtype, n, block, compute_units=0):
     r, s, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
     check(lib.ek_hip_reduce_blocks_plan(NP2EK[np.dtype(dtype)], ctypes.c_size_t(n), ctypes.c_size_t(block), int(compute_units),
                                         ctypes.byref(r), ctypes.byref(s), ctypes.byref(w)))
+    return r.value, s.value, w.value
+
+
+SCAN_EXCLUSIVE, SCAN_REVERSE = 1, 2
+
+
+def psum_blocks(a, block, exclusive=False, reverse=False, out=None):
+    """per-block prefix sums of the a.n / block blocks of `block` entries (ek_hip_psum_blocks): out[j * block + k] is the sum of
+    entries 0 .. k of block j, 0 .. k - 1 with `exclusive`, k .. block - 1 with `reverse`; `out`: write into this array (may be `a`)"""
+    if out is None:
+        out = Buf(a.dtype, a.n)
+    flags = (SCAN_EXCLUSIVE if exclusive else 0) | (SCAN_REVERSE if reverse else 0)
+    check(lib.ek_hip_psum_blocks(a.ek, ctypes.c_void_p(out.ptr if a.n else None), ctypes.c_void_p(a.ptr if a.n else None),
+                                 ctypes.c_size_t(a.n), ctypes.c_size_t(int(block)), flags))
+    return out
+
+
+def psum_blocks_plan(dtype, n, block, compute_units=0):
+    """(regime, splits, workgroups): the route ek_hip_psum_blocks takes for n entries of `dtype` in blocks of `block` (host only).
+    regime: 0 copy or zero fill, 1 packed, 2 one workgroup per block, 3 split into `splits` pieces per block"""
+    r, s, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
+    check(lib.ek_hip_psum_blocks_plan(NP2EK[np.dtype(dtype)], ctypes.c_size_t(n), ctypes.c_size_t(block), int(compute_units),
+                                      ctypes.byref(r), ctypes.byref(s), ctypes.byref(w)))
     return r.value, s.value, w.value
 
 

@@ -252,6 +252,10 @@ template <typename Array> py::class_<Array> bind_array(py::module_ &m, const cha
         m.def("block_min", [](const Array &a, size_t block) { return block_min(a, block); }, "array"_a, "block"_a);
         m.def("block_max", [](const Array &a, size_t block) { return block_max(a, block); }, "array"_a, "block"_a);
         m.def("repeat", [](const Array &a, size_t block) { return repeat(a, block); }, "array"_a, "block"_a);
+        // prefix sums inside every block: entry k of a block is the sum of its entries 0 .. k (0 .. k - 1 with exclusive, from the
+        // block's end with reverse); differentiable
+        m.def("block_psum", [](const Array &a, size_t block, bool exclusive, bool reverse) { return block_psum(a, block, exclusive, reverse); },
+              "array"_a, "block"_a, "exclusive"_a = false, "reverse"_a = false);
     }
 
     if constexpr (IsFloat) {

@@ -566,6 +566,40 @@ template <typename Value> auto Tape<Value>::append_repeat(Index source, size_t b
     return target;
 }
 
+// block_psum: out[k] collects the entries of its block at or before k (before k: exclusive; at or after k: reverse), so entry i
+// reaches exactly the outputs on its other side: the adjoint is the same scan with the direction flipped and `exclusive` kept.  One
+// Special serves all four flag combinations; forward applies the node's own scan to the source's gradient.  A size-1 gradient is a
+// broadcast seed and is widened first, as in BlockTranspose.
+namespace detail {
+    template <typename TapeT, typename Value> struct BlockPrefixSum : TapeT::Special {
+        size_t block;
+        bool exclusive, reverse;
+        BlockPrefixSum(size_t block, bool exclusive, bool reverse) : block(block), exclusive(exclusive), reverse(reverse) { }
+        Value apply(Value g, size_t size, bool rev) const {
+            if (g.size() == 1 && size != 1) set_slices(g, size);
+            return block_psum(g, block, exclusive, rev);
+        }
+        void forward(typename TapeT::Detail *detail, typename TapeT::Index target, const typename TapeT::Edge &edge) const override {
+            auto &s = detail->node(edge.source);
+            TapeT::Detail::accumulate(detail->node(target).grad, apply(s.grad, s.size, reverse));
+        }
+        void backward(typename TapeT::Detail *detail, typename TapeT::Index target, const typename TapeT::Edge &edge) const override {
+            auto &t = detail->node(target);
+            TapeT::Detail::accumulate(detail->node(edge.source).grad, apply(t.grad, t.size, !reverse));
+        }
+    };
+}
+
+template <typename Value> auto Tape<Value>::append_block_psum(Index source, size_t block, bool exclusive, bool reverse) -> Index {
+    if (source == 0) return 0;
+    const size_t size = d->node(source).size;
+    if (block == 0 || size % block != 0) throw std::runtime_error("Tape::append_block_psum(): the source is no whole number of blocks");
+    Index target = append_node(size, "block_psum");
+    d->node(target).edges.emplace_back(source, new detail::BlockPrefixSum<Tape, Value>(block, exclusive, reverse));
+    inc_ref_int(source, target);
+    return target;
+}
+
 // ---------------------------------------------------------------------------------------------
 //  Reference counting (autodiff.cpp:681-774)
 // ---------------------------------------------------------------------------------------------

@@ -1662,6 +1662,22 @@ ENOKI_HIP_BLOCK_OP(block_sum) ENOKI_HIP_BLOCK_OP(block_prod) ENOKI_HIP_BLOCK_OP(
 ENOKI_HIP_BLOCK_OP(repeat)
 #undef ENOKI_HIP_BLOCK_OP
 
+/// Prefix sums inside every block of `block` consecutive entries of a flat array (size(x) is a multiple of block):
+/// block_psum(x, B)[j * B + k] = x[j * B] + .. + x[j * B + k]; with `exclusive` the sum stops before entry k (the first entry of a
+/// block is +0), with `reverse` it runs from the block's end: x[j * B + k] + .. + x[(j + 1) * B - 1].  The optical depth in front
+/// of every sample of a ray is block_psum(sigma * dt, S, true).  One pass, nothing subtracted, bit-identical from run to run,
+/// differentiable in both modes (the adjoint is the same scan from the other end).  An array type without the member throws.
+namespace detail {
+    template <typename T, typename = void> struct has_block_psum : std::false_type { };
+    template <typename T> struct has_block_psum<T, std::void_t<decltype(std::declval<const T &>().block_psum_(size_t(1), false, false))>>
+        : std::true_type { };
+}
+template <typename T> inline T block_psum(const T &x, size_t block, bool exclusive = false, bool reverse = false) {
+    static_assert(array_depth_v<T> == 1, "block_psum(): takes a flat array");
+    if constexpr (detail::has_block_psum<T>::value) return x.block_psum_(block, exclusive, reverse);
+    else throw std::runtime_error("block_psum(): not available for this array type");
+}
+
 /// Angle between two unit vectors / between a unit vector and the z axis, well behaved near 0 and pi (array_math.h:1404-1436)
 template <typename T> inline auto unit_angle(const T &a, const T &b) {
     auto dot_uv = dot(a, b);

@@ -128,6 +128,8 @@ template <typename Type> struct Tape {
     Index append_block_sum(Index source, size_t block);
     /// repeat(source, block): every entry `block` times in a row; its adjoint is block_sum()
     Index append_repeat(Index source, size_t block);
+    /// block_psum(source, block, exclusive, reverse): prefix sums inside every block; its adjoint is the same scan from the other end
+    Index append_block_psum(Index source, size_t block, bool exclusive, bool reverse);
     void set_scatter_gather_operand(Index *index, size_t size, bool permute);
 
     // ---- reference counting (ext = held by DiffArray handles, int = held by graph edges) ----
@@ -781,6 +783,16 @@ template <typename Type_> struct DiffArray : ArrayTag {
         Index idx = 0;
         if constexpr (Enabled) {
             if (m_index) idx = tape()->append_repeat(m_index, block);
+        }
+        return create(idx, std::move(result));
+    }
+
+    /// Prefix sums inside every block of `block` consecutive entries: one tape node of the source's size (Tape::append_block_psum)
+    DiffArray block_psum_(size_t block, bool exclusive, bool reverse) const {
+        Type result = block_psum(m_value, block, exclusive, reverse);
+        Index idx = 0;
+        if constexpr (Enabled) {
+            if (m_index) idx = tape()->append_block_psum(m_index, block, exclusive, reverse);
         }
         return create(idx, std::move(result));
     }

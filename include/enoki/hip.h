@@ -1787,6 +1787,25 @@ template <typename Value_> struct HIPArray : ArrayTag {
         return r;
     }
 
+    /// Prefix sums inside every block of `block` consecutive entries (ek_hip_psum_blocks): entry k of a block becomes the sum of
+    /// its entries 0 .. k, 0 .. k - 1 with `exclusive` (the empty sum is +0), k .. block - 1 with `reverse`.  An unevaluated
+    /// operand is evaluated once; a host scalar is an array of one entry.
+    HIPArray block_psum_(size_t block, bool exclusive, bool reverse) const {
+        static_assert(!IsMask, "block_psum_(): not defined for masks");
+        const size_t n = size();
+        if (block == 0 || n % block != 0)
+            throw std::runtime_error("HIPArray::block_psum_(): " + std::to_string(n) + " entries are no whole number of blocks of " +
+                                     std::to_string(block));
+        if (!&ek_hip_psum_blocks)
+            throw std::runtime_error("HIPArray::block_psum_(): this C ABI has no entry ek_hip_psum_blocks");
+        if (n == 0) return HIPArray();
+        materialize();
+        HIPArray r = empty_(n);
+        detail::hip_check(ek_hip_psum_blocks(Type, r.m_buf->ptr, ptr_(), n, block,
+                                             (exclusive ? EK_SCAN_EXCLUSIVE : 0) | (reverse ? EK_SCAN_REVERSE : 0)), "block_psum_");
+        return r;
+    }
+
     // -----------------------------------------------------------------------------------------
     //  Storage access
     // -----------------------------------------------------------------------------------------

@@ -574,6 +574,34 @@ EK_API EK_OPTIONAL int ek_hip_reduce_blocks_plan(int type, size_t n, size_t bloc
  * gather(v, arange(m * block) / block).  Keyed on the element size: I32 .. F64.  block == 0: EK_ERR_INVALID; m == 0: nothing is
  * launched; block == 1 is a device copy.  16-byte stores wherever `out` allows; one division per lane.  EK_OPTIONAL as above. */
 EK_API EK_OPTIONAL int ek_hip_repeat(int type, void *out, const void *in, size_t m, size_t block);
+/* Per-block prefix sums: for block j < n / block and position k < block, with x = in + j * block,
+ *     out[j * block + k] = x[0] + .. + x[k]            flags == 0
+ *                          x[0] + .. + x[k - 1]        EK_SCAN_EXCLUSIVE
+ *                          x[k] + .. + x[block - 1]    EK_SCAN_REVERSE
+ *                          x[k + 1] + .. + x[block-1]  EK_SCAN_EXCLUSIVE | EK_SCAN_REVERSE
+ * the empty sum being +0 (+0.0) -- the optical depth in front of every sample of a ray, the per-row CDFs of a row-major table,
+ * running counts inside a segment -- in one pass, where psum(x) - repeat(gather(psum(x), block starts), block) takes four and
+ * subtracts two large sums to get a small one.  I32 .. F64 (EK_BOOL or an unknown type: EK_ERR_UNSUPPORTED); integer sums wrap.
+ * block == 0, n % block != 0, a null pointer with n > 0 or a flag bit other than the two: EK_ERR_INVALID; n == 0: nothing is
+ * launched.  The pointers need only element alignment; out and in are identical or do not overlap.  Guarantees:
+ *   - every output is a sum of its own terms only: nothing is ever subtracted, an exclusive result is not "inclusive minus x";
+ *   - an inclusive entry with one term is that input bit for bit, -0.0 included;
+ *   - an exclusive entry k is bit for bit the inclusive entry k - 1 of the same array (k + 1 for EK_SCAN_REVERSE);
+ *   - no value of one block ever reaches another block's output: a NaN or an infinity in block j leaves blocks j - 1 and j + 1 alone;
+ *   - the shape of every sum is fixed by (type, n, block, flags, pointer alignment, number of compute units): the result is
+ *     bit-identical from run to run;
+ *   - no atomics on data, no read-back, no host wait: the call can be captured into a step graph; scratch comes from ek_hip_malloc
+ *     and is freed stream-ordered;
+ *   - no kernel waits for another workgroup -- no ticket, no descriptor, no look-back, no polling loop: what one workgroup needs
+ *     from another is a separate launch on the stream, so no kernel of this entry can spin.
+ * ek_hip_psum_blocks_plan (host only, no device access; compute_units == 0: 256) reports the route: *regime 0 copy or zero fill
+ * (block == 1), 1 packed (block <= 1024: tiles of whole blocks scanned in LDS), 2 one workgroup per block, 3 split (fewer than
+ * 2 x compute_units blocks of at least 16 Ki entries: *splits >= 2 pieces per block, their totals, an exclusive scan of the
+ * totals, the pieces with their carry-in; *splits == 1 otherwise), and *workgroups, the grid of its first launch.
+ * EK_OPTIONAL: enoki/hip.h asks for the entries' addresses first and throws without them. */
+enum { EK_SCAN_EXCLUSIVE = 1, EK_SCAN_REVERSE = 2 };
+EK_API EK_OPTIONAL int ek_hip_psum_blocks(int type, void *out, const void *in, size_t n, size_t block, int flags);
+EK_API EK_OPTIONAL int ek_hip_psum_blocks_plan(int type, size_t n, size_t block, int compute_units, int *regime, int *splits, size_t *workgroups);
 
 /* Stable sort of (key, element number) pairs by the low `key_bits` bits of 32-bit keys:
  *     keys_out = keys sorted ascending, perm_out[j] = original position of keys_out[j]; equal keys keep their order.
