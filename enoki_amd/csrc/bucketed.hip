@@ -437,10 +437,13 @@ void ek_hip_bucket_partition::free_storage() {
         meta_slot = -1;
         meta = nullptr;
     }
-    for (void **p : { &meta, &pair_idx, &x_b, &page_lists }) {
+    for (void **p : { &meta, &pair_idx, &x_b, &page_lists, &refined }) {
         if (*p) ek_hip_free(*p);
         *p = nullptr;
     }
+    refined_x = nullptr; refined_hdr = nullptr; refined_tiles = nullptr;
+    refined_cap_tiles = 0; refined_bytes = 0;
+    refine_state = -1;             // (what the stream was made from is gone)
 }
 namespace ek {
 
@@ -458,7 +461,7 @@ size_t evict_idle_partitions() {
     size_t bytes = 0;
     for (BucketPartition *p : live_partitions()) {
         if (p->objects || p->evicted) continue;
-        bytes += p->positions * (sizeof(uint16_t) + sizeof(float));
+        bytes += p->positions * (sizeof(uint16_t) + sizeof(float)) + p->refined_bytes;
         p->free_storage();
         p->evicted = true;
     }
@@ -1929,6 +1932,7 @@ int ek_hip_bucketed_pair_create_on(ek_hip_bucket_partition *p, int type, int ind
     b->glist_full = p->glist_full; b->glist_part = p->glist_part;
     b->active = p->active; b->ticket = p->ticket; b->reduce_partials = p->reduce_partials;
     b->part = p;
+    b->stands_on_kept = true;
     *out = b;
     return EK_OK;
 }

@@ -1,6 +1,7 @@
 // The reduction of f(u) AND the adjoint of the two gathers in ONE pass over a bucket's elements (the headline step's second big
 // kernel).  See bucketed.hip for the path as a whole; what the translation units share is in ek_bucketed.h.
 #include "ek_bucketed.h"
+#include "ek_refine.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -343,6 +344,111 @@ __device__ __forceinline__ void walk_pages_dynamic(const BucketLists &bl, const 
 }
 
 
+// ---- the same sums from the REFINED stream of a kept partition (ek_refine.h, bucket_refine.hip) --------------------------------
+// The piece's elements once more, in entry order, four to a group that shares ONE entry: a step of a lane is one 16-byte x load and
+// one 2-byte header, ONE record read, four times u / sincos / conversion as above, the four terms of each plane added as integers
+// in registers, and TWO ds_add_u64 -- instead of four record reads and eight adds.  Every term is rounded by itself, exactly as in
+// EarlyFixed::apply, and 64-bit integer addition is associative: the sums and y are bit for bit those of the page walk.  The lanes
+// of one LDS instruction address neighbouring entries (lane i owns R consecutive groups of the sorted order), not random ones.
+/// where the stream is: null pointers in the kernels that walk the pages
+struct RefinedStream {
+    const float *x;
+    const uint16_t *hdr;
+    const uint32_t *tiles;               // [pieces + 1]: the pieces' first tiles
+    uint32_t cap_tiles;                  // tiles the storage holds (nothing is read beyond them)
+};
+struct NoRefinedStream { };              // what the kernels that walk the pages take in its place
+template <bool Refined> using RefinedArg = std::conditional_t<Refined, RefinedStream, NoRefinedStream>;
+
+template <int Map, int Keep, bool Two>
+struct EarlyRefined {
+    using T = float;
+    struct Step { uint32_t h; T px[4]; };
+    struct Recs { uint32_t a8; PairRec<T> r; };
+    const unsigned char *lds;
+    uint32_t m8;
+    double up0, up1;
+    long long iacc;
+
+    __device__ __forceinline__ void lookup(const Step &s, Recs &o) const {
+        o.a8 = (s.h << 3) & m8;                                  // (the count bits lie above the mask: Bins <= 4 Ki)
+        o.r = *reinterpret_cast<const PairRec<T> *>(lds + o.a8);
+    }
+    __device__ __forceinline__ void apply(const Step &s, const Recs &rc) {
+        const int count = (int) (s.h >> kRefineEntryBits);
+        int batch = 0;
+        unsigned long long s0 = 0ull, s1 = 0ull;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const T x = s.px[k];
+            const T u = pair_value(rc.r.a, x, rc.r.c, Two);
+            T sn = T(0), cs = T(0);
+            dev::sincos_f32<Map == EK_SIN || Keep == EK_SIN, Map == EK_COS || Keep == EK_COS, true>(u, sn, cs);
+            const T sum = Map == EK_SIN ? sn : cs;
+            T v0 = Keep == EK_SIN ? sn : cs;
+            int q = dev::cvt_sat_i32(sum * 268435456.0f);
+            // a pad lane (beyond the group's count; its x is 0): the masked form of EarlyFixed::apply
+            const bool on = k < count;
+            q = on ? q : 0;
+            v0 = on ? v0 : T(0);
+            batch += q;
+            const T v1 = dev::safe_mul(x, v0);
+            s0 += to_fixed64(v0, up0);
+            s1 += to_fixed64(v1, up1);
+        }
+        unsigned long long *p = reinterpret_cast<unsigned long long *>(const_cast<unsigned char *>(lds) + kFixedRecBytes + rc.a8);
+        unsigned long long *p1 = reinterpret_cast<unsigned long long *>(const_cast<unsigned char *>(lds) + 2 * kFixedRecBytes + rc.a8);
+        (void) __hip_atomic_fetch_add(p, s0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        (void) __hip_atomic_fetch_add(p1, s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        iacc += (long long) batch;
+    }
+};
+
+/// tiles [t0, t1) of a piece handed to the waves from `s_next` (initialised to 2 * kBucketWaves: a wave's first two tiles are wave and
+/// wave + 16).  A step moves through three stages as in walk_pages_dynamic: (header, x) loads THREE steps ahead, the record read one
+/// step ahead, arithmetic + adds; the four step buffers and two record sets change roles instead of being copied.  The steps behind a
+/// wave's last tile load the tile once more (valid memory) and are not applied.
+template <typename Body>
+__device__ __forceinline__ void walk_tiles_dynamic(const RefinedStream &rs, uint32_t t0, uint32_t t1, Body &body, uint32_t *s_next) {
+    using Step = typename Body::Step;
+    constexpr uint32_t R = kRefineR;
+    static_assert(R % 4 == 0);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nt = t1 - t0;
+    uint32_t tile0 = wave, tile1 = wave + kBucketWaves;
+    if (tile0 >= nt) return;
+    auto fetch = [&](Step &s, uint32_t tile, uint32_t g) {
+        const size_t slot = ((size_t) (t0 + tile) * R + g) * 64u + lane;
+        s.h = (uint32_t) __builtin_nontemporal_load(rs.hdr + slot);
+        load4<float, true>(rs.x + slot * 4u, s.px);
+    };
+    Step st0, st1, st2, st3;
+    typename Body::Recs r0, r1;
+    fetch(st0, tile0, 0);
+    fetch(st1, tile0, 1);
+    fetch(st2, tile0, 2);
+    body.lookup(st0, r0);
+    while (true) {
+        uint32_t g2 = 0;
+        if (lane == 0) g2 = __hip_atomic_fetch_add(s_next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);     // two tiles ahead
+        const uint32_t tnext = tile1 < nt ? tile1 : tile0;
+        auto phase = [&](uint32_t g, const Step &cur, const Step &next, Step &last, const typename Body::Recs &rc, typename Body::Recs &rn) {
+            const uint32_t gf = g + 3u;
+            fetch(last, gf < R ? tile0 : tnext, gf & (R - 1u));
+            body.lookup(next, rn);
+            body.apply(cur, rc);
+        };
+        for (uint32_t g = 0; g < R; g += 4) {
+            phase(g, st0, st1, st3, r0, r1);
+            phase(g + 1, st1, st2, st0, r1, r0);
+            phase(g + 2, st2, st3, st1, r0, r1);
+            phase(g + 3, st3, st0, st2, r1, r0);
+        }
+        tile0 = tile1;
+        tile1 = (uint32_t) __builtin_amdgcn_readfirstlane((int) g2);
+        if (tile0 >= nt) break;
+    }
+}
+
 /// bucket_finish for the fixed-point kernel: every workgroup publishes an INTEGER partial (units of 2^-28; pieces that ran under locks: 0)
 /// and a float one (pieces under locks; 0 otherwise); the last workgroup adds the integers exactly -- the order cannot matter --,
 /// converts once, and adds the float partials in the order of the pieces.
@@ -404,7 +510,7 @@ __device__ __forceinline__ void bucket_finish_fixed_end(const uint32_t *s_last_f
 // The body of the two kernels below.  addend / zero_op / zero_u: what is staged without an addend table, and what a dropped lane
 // contributes (map zero_op of zero_u) -- compile-time constants in k_bucket_pair_forward_adjoint (-0.0 and zero_op(0), folded), run-time
 // values in k_bucket_pair_forward_adjoint_scalar.
-template <typename T, int V, int PS, bool Fixed, bool Two>
+template <typename T, int V, int PS, bool Fixed, bool Two, bool Refined>
 __device__ __forceinline__ void bucket_pair_forward_adjoint(T *__restrict__ partials, T *__restrict__ table_partials,
                                                             const T *__restrict__ table_a, const T *__restrict__ table_c, const T addend,
                                                             size_t table_size, int flip_a, int flip_c,
@@ -412,7 +518,8 @@ __device__ __forceinline__ void bucket_pair_forward_adjoint(T *__restrict__ part
                                                             const BucketLists &bl, int map_op, int keep_op, int shift,
                                                             const BucketFinish<T> &fin, const int zero_op, const T zero_u,
                                                             const uint32_t *__restrict__ xmax_bits, int S0,
-                                                            uint32_t *__restrict__ piece_mode) {
+                                                            uint32_t *__restrict__ piece_mode, const RefinedArg<Refined> &refined) {
+    static_assert(!Refined || (Fixed && sizeof(T) == 4), "the refined stream feeds the fixed-point walk only");
     extern __shared__ __align__(16) unsigned char lds_dynamic[];
     // Fixed: a STATIC block (records of 4 Ki entries + 4 Ki pairs of sums, whatever Bins is) -- its address is a constant of the
     // program, every LDS instruction of the walk carries it in its immediate offset
@@ -435,10 +542,14 @@ __device__ __forceinline__ void bucket_pair_forward_adjoint(T *__restrict__ part
     const unsigned long long t_entry = __builtin_readcyclecounter();
 #endif
     // (asked for before anything depends on it: a dependent round trip behind the staging barrier otherwise)
-    [[maybe_unused]] uint32_t xm_early = 0;
+    [[maybe_unused]] uint32_t xm_early = 0, tile_first = 0, tile_end = 0;
+    if constexpr (Refined) {
+        tile_first = min(refined.tiles[blockIdx.x], refined.cap_tiles);
+        tile_end = min(refined.tiles[blockIdx.x + 1], refined.cap_tiles);
+    }
     if constexpr (Fixed) {
         xm_early = xmax_bits[0];
-        if (threadIdx.x == 0) { s_next = 5u * kBucketWaves; s_guard[0] = 0u; s_guard[1] = 0u; }       // (ordered before their users by bucket_piece's barrier)
+        if (threadIdx.x == 0) { s_next = (Refined ? 2u : 5u) * kBucketWaves; s_guard[0] = 0u; s_guard[1] = 0u; }       // (ordered before their users by bucket_piece's barrier)
     }
     if (!bucket_piece<PS>(bl, bucket, range)) {
         if constexpr (Fixed) {
@@ -537,7 +648,24 @@ __device__ __forceinline__ void bucket_pair_forward_adjoint(T *__restrict__ part
 #endif
                 iv = body.iacc;
             };
+            // the same piece from the refined stream: its tiles instead of its pages
+            [[maybe_unused]] auto run_refined = [&](auto body) {
+                if constexpr (Refined) {
+                    body.lds = lds_raw;
+                    asm volatile("v_mov_b32 %0, %1" : "=v"(body.m8) : "s"(((uint32_t) Bins - 1u) << 3));
+                    body.up0 = fixed0.upd; body.up1 = fixed1.upd; body.iacc = 0;
+                    walk_tiles_dynamic(refined, (uint32_t) __builtin_amdgcn_readfirstlane((int) tile_first),
+                                       (uint32_t) __builtin_amdgcn_readfirstlane((int) tile_end), body, &s_next);
+                    iv = body.iacc;
+                }
+            };
             // (launched for the pairs whose functions are bounded by 1 only: bucketed_forward_adjoint_launch)
+            if constexpr (Refined) {
+                if (map_op == EK_SIN && keep_op == EK_COS) run_refined(EarlyRefined<EK_SIN, EK_COS, Two>{});
+                else if (map_op == EK_COS && keep_op == EK_SIN) run_refined(EarlyRefined<EK_COS, EK_SIN, Two>{});
+                else if (map_op == EK_SIN) run_refined(EarlyRefined<EK_SIN, EK_SIN, Two>{});
+                else run_refined(EarlyRefined<EK_COS, EK_COS, Two>{});
+            } else
             if (map_op == EK_SIN && keep_op == EK_COS) run_fixed(EarlyFixed<PS, EK_SIN, EK_COS, Two>{});
             else if (map_op == EK_COS && keep_op == EK_SIN) run_fixed(EarlyFixed<PS, EK_COS, EK_SIN, Two>{});
             else if (map_op == EK_SIN) run_fixed(EarlyFixed<PS, EK_SIN, EK_SIN, Two>{});
@@ -636,7 +764,7 @@ __device__ __forceinline__ void bucket_pair_forward_adjoint(T *__restrict__ part
 
 // Two tables, or the product alone: the arguments, the staged -0.0 and the dropped lanes' folded zero_op(0) of the kernel as it was
 // before a host scalar could be the addend -- the headline step runs THIS kernel (fin.zero_u is not looked at).
-template <typename T, int V, int PS, bool Fixed, bool Two>
+template <typename T, int V, int PS, bool Fixed, bool Two, bool Refined>
 __global__ __launch_bounds__(kBucketThreads) void k_bucket_pair_forward_adjoint(T *__restrict__ partials, T *__restrict__ table_partials,
                                                                                 const T *__restrict__ table_a,
                                                                                 const T *__restrict__ table_c, size_t table_size,
@@ -645,16 +773,16 @@ __global__ __launch_bounds__(kBucketThreads) void k_bucket_pair_forward_adjoint(
                                                                                 const T *__restrict__ x_b, BucketLists bl,
                                                                                 int map_op, int keep_op, int shift, BucketFinish<T> fin,
                                                                                 const uint32_t *__restrict__ xmax_bits, int S0,
-                                                                                uint32_t *__restrict__ piece_mode) {
-    bucket_pair_forward_adjoint<T, V, PS, Fixed, Two>(partials, table_partials, table_a, table_c, T(-0.0), table_size, flip_a, flip_c, pair_idx,
-                                                      x_b, bl, map_op, keep_op, shift, fin, fin.zero_op, T(0), xmax_bits, S0, piece_mode);
+                                                                                uint32_t *__restrict__ piece_mode, RefinedArg<Refined> refined) {
+    bucket_pair_forward_adjoint<T, V, PS, Fixed, Two, Refined>(partials, table_partials, table_a, table_c, T(-0.0), table_size, flip_a, flip_c, pair_idx,
+                                                               x_b, bl, map_op, keep_op, shift, fin, fin.zero_op, T(0), xmax_bits, S0, piece_mode, refined);
 }
 
 // A host-scalar addend (no addend table): the scalar and the dropped lanes' u are kernel arguments.  The fixed-point instantiations
 // sit AT the limit of scalar registers (106): the two sign flags travel as one argument (1: -a, 2: -c) and the dropped lanes'
 // function is map_op itself -- this kernel does not look at fin.zero_op, the launch below asserts that the two agree -- which pays
 // for the two new values (without: 103 VGPRs, two scalar registers spilled).
-template <typename T, int V, int PS, bool Fixed, bool Two>
+template <typename T, int V, int PS, bool Fixed, bool Two, bool Refined>
 __global__ __launch_bounds__(kBucketThreads) void k_bucket_pair_forward_adjoint_scalar(T *__restrict__ partials, T *__restrict__ table_partials,
                                                                                        const T *__restrict__ table_a, T addend,
                                                                                        size_t table_size, int flips,
@@ -662,9 +790,9 @@ __global__ __launch_bounds__(kBucketThreads) void k_bucket_pair_forward_adjoint_
                                                                                        const T *__restrict__ x_b, BucketLists bl,
                                                                                        int map_op, int keep_op, int shift, BucketFinish<T> fin,
                                                                                        const uint32_t *__restrict__ xmax_bits, int S0,
-                                                                                       uint32_t *__restrict__ piece_mode) {
-    bucket_pair_forward_adjoint<T, V, PS, Fixed, Two>(partials, table_partials, table_a, nullptr, addend, table_size, flips & 1, flips & 2, pair_idx,
-                                                      x_b, bl, map_op, keep_op, shift, fin, map_op, fin.zero_u, xmax_bits, S0, piece_mode);
+                                                                                       uint32_t *__restrict__ piece_mode, RefinedArg<Refined> refined) {
+    bucket_pair_forward_adjoint<T, V, PS, Fixed, Two, Refined>(partials, table_partials, table_a, nullptr, addend, table_size, flips & 1, flips & 2, pair_idx,
+                                                               x_b, bl, map_op, keep_op, shift, fin, map_op, fin.zero_u, xmax_bits, S0, piece_mode, refined);
 }
 
 template <typename T>
@@ -688,39 +816,70 @@ int bucketed_forward_adjoint_launch(Bucketed *b, void *out, int map_op, int keep
     const int S0 = std::min(fixed_shift_for(piece_bound), 48);
     uint32_t *modes = fixed ? reinterpret_cast<uint32_t *>(static_cast<char *>(b->early) + (size_t) 2 * b->max_pieces * Bins * slot) : nullptr;
     const bool scalar = b->scalar_addend;
+    // A kept partition that this object found in its caller's cache (a hit) gets its refined stream here, once, outside a capture;
+    // the kernel that reads it runs whenever the partition has one -- the scalar-addend kernel too: its refined instantiations fit
+    // (106 scalar registers, 121 vector registers, no scratch, no spill: profiles/kernel_resources_refine_r14.txt).
+    const bool eager = refuse_while_capturing_quiet() == EK_OK;
+    if (fixed && eager && b->part && b->stands_on_kept && b->part->refine_state == 0 && Bins <= ((size_t) 1 << kRefineEntryBits))
+        if (int rc = partition_refine(b->part)) return rc;
+    const bool use_refined = fixed && eager && b->part && b->part->refine_state == 1;
     const uint32_t *xmax = fixed ? b->active + (kPgMetaResultXmax - kPgMetaResult) : nullptr;
-    auto go = [&](auto kernel, auto kernel_scalar) -> int {
+    auto go = [&](auto kernel, auto kernel_scalar, auto kernel_refined, auto kernel_scalar_refined) -> int {
         if (int rc = scalar ? allow_big_lds(kernel_scalar, lds) : allow_big_lds(kernel, lds)) return rc;
         const BucketFinish<T> fin = b->template finish<T>(out, map_op);
+        if constexpr (!std::is_same_v<decltype(kernel_refined), std::nullptr_t>) {
+            const BucketPartition *p = b->part;
+            if (use_refined && scalar) {
+                if (fin.zero_op != map_op || b->table_c) return fail(EK_ERR_INVALID, "bucketed_forward_adjoint_launch(): inconsistent scalar-addend object");
+                hipLaunchKernelGGL(kernel_scalar_refined, dim3(b->max_pieces), dim3(kBucketThreads), lds, c.stream,
+                                   (T *) b->reduce_partials, (T *) b->early, (const T *) b->table_a, b->template addend<T>(), b->table_size,
+                                   flip_a | (flip_c << 1), (const uint16_t *) b->pair_idx, (const T *) b->x_b, b->lists(), map_op, keep_op, b->shift,
+                                   fin, xmax, S0, modes, RefinedStream{ p->refined_x, p->refined_hdr, p->refined_tiles, p->refined_cap_tiles });
+                return EK_OK;
+            }
+            if (use_refined) {
+                hipLaunchKernelGGL(kernel_refined, dim3(b->max_pieces), dim3(kBucketThreads), lds, c.stream,
+                                   (T *) b->reduce_partials, (T *) b->early, (const T *) b->table_a, (const T *) b->table_c, b->table_size,
+                                   flip_a, flip_c, (const uint16_t *) b->pair_idx, (const T *) b->x_b, b->lists(), map_op, keep_op, b->shift,
+                                   fin, xmax, S0, modes, RefinedStream{ p->refined_x, p->refined_hdr, p->refined_tiles, p->refined_cap_tiles });
+                return EK_OK;
+            }
+        }
         if (scalar) {
             // (k_bucket_pair_forward_adjoint_scalar applies map_op to the dropped lanes' u without looking at fin.zero_op)
             if (fin.zero_op != map_op || b->table_c) return fail(EK_ERR_INVALID, "bucketed_forward_adjoint_launch(): inconsistent scalar-addend object");
             hipLaunchKernelGGL(kernel_scalar, dim3(b->max_pieces), dim3(kBucketThreads), lds, c.stream,
                                (T *) b->reduce_partials, (T *) b->early, (const T *) b->table_a, b->template addend<T>(), b->table_size,
                                flip_a | (flip_c << 1), (const uint16_t *) b->pair_idx, (const T *) b->x_b, b->lists(), map_op, keep_op, b->shift,
-                               fin, xmax, S0, modes);
+                               fin, xmax, S0, modes, NoRefinedStream{});
         } else {
             hipLaunchKernelGGL(kernel, dim3(b->max_pieces), dim3(kBucketThreads), lds, c.stream,
                                (T *) b->reduce_partials, (T *) b->early, (const T *) b->table_a, (const T *) b->table_c, b->table_size,
                                flip_a, flip_c, (const uint16_t *) b->pair_idx, (const T *) b->x_b, b->lists(), map_op, keep_op, b->shift,
-                               fin, xmax, S0, modes);
+                               fin, xmax, S0, modes, NoRefinedStream{});
         }
         return EK_OK;
     };
-#define EK_PAIR(PSV, FIXED, TWO) go(k_bucket_pair_forward_adjoint<T, VV, PSV, FIXED, TWO>, k_bucket_pair_forward_adjoint_scalar<T, VV, PSV, FIXED, TWO>)
+#define EK_PAIR(PSV, FIXED, TWO) go(k_bucket_pair_forward_adjoint<T, VV, PSV, FIXED, TWO, false>, k_bucket_pair_forward_adjoint_scalar<T, VV, PSV, FIXED, TWO, false>, nullptr, nullptr)
+#define EK_PAIR_FIXED(PSV, TWO) go(k_bucket_pair_forward_adjoint<T, VV, PSV, true, TWO, false>, k_bucket_pair_forward_adjoint_scalar<T, VV, PSV, true, TWO, false>, \
+                                   k_bucket_pair_forward_adjoint<T, VV, PSV, true, TWO, true>, k_bucket_pair_forward_adjoint_scalar<T, VV, PSV, true, TWO, true>)
     int rc;
     if constexpr (sizeof(T) == 8) {
         rc = two ? EK_PAIR(0, false, true) : EK_PAIR(0, false, false);
     } else {
         if (fixed) lds = 0;            // (the fixed-point kernels' LDS is static)
-#define EK_GO(PSV) (fixed ? (two ? EK_PAIR(PSV, true, true) : EK_PAIR(PSV, true, false)) : (two ? EK_PAIR(PSV, false, true) : EK_PAIR(PSV, false, false)))
+#define EK_GO(PSV) (fixed ? (two ? EK_PAIR_FIXED(PSV, true) : EK_PAIR_FIXED(PSV, false)) : (two ? EK_PAIR(PSV, false, true) : EK_PAIR(PSV, false, false)))
         rc = b->page_shift == 6 ? EK_GO(6) : EK_GO(5);
 #undef EK_GO
     }
 #undef EK_PAIR
+#undef EK_PAIR_FIXED
     if (rc) return rc;
+    // (the pages: 6 B per element; the refined stream: 18 B per group of four, an entry's last group 3/8 empty on average -- what
+    //  the host can say without a read-back)
+    const size_t stream_bytes = use_refined ? 18u * (b->n / 4u + 3u * std::min(b->n, b->table_size) / 8u) : b->n * (sizeof(uint16_t) + sizeof(T));
     EK_LAUNCH_CHECK("bucket_pair_fma_reduce_adjoint", b->n,
-                    b->n * (sizeof(uint16_t) + sizeof(T)) + (b->table_c ? 2 : 1) * b->table_size * sizeof(T) + (size_t) 2 * b->max_pieces * Bins * slot);
+                    stream_bytes + (b->table_c ? 2 : 1) * b->table_size * sizeof(T) + (size_t) 2 * b->max_pieces * Bins * slot);
     b->launched_reducing();
     b->early_fixed = fixed;
     b->early_S0 = S0;

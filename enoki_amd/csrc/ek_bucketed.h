@@ -639,6 +639,15 @@ struct ek_hip_bucket_partition {
     const uint32_t *active = nullptr;
     uint32_t *ticket = nullptr;
     void *reduce_partials = nullptr;
+    // the refined stream (ek_refine.h): the same elements, the same pieces, in entry order and in groups of four -- built at the first
+    // launch of an object that stands on the kept partition (partition_refine(), bucket_refine.hip), freed with the rest
+    int refine_state = 0;          // 0: not decided yet, 1: built, -1: none (switched off, too sparse, no memory: the reason went to the log)
+    void *refined = nullptr;       // ONE allocation: x (16 B per group) | headers (2 B per group) | tile offsets [max_pieces + 1]
+    float *refined_x = nullptr;
+    uint16_t *refined_hdr = nullptr;
+    uint32_t *refined_tiles = nullptr;
+    uint32_t refined_cap_tiles = 0;
+    size_t refined_bytes = 0;
     void free_storage();           // bucketed.hip: the ring block back to the ring (with its `clean` state), the rest to the allocator
     ~ek_hip_bucket_partition() { free_storage(); }
 };
@@ -647,6 +656,8 @@ using BucketPartition = ::ek_hip_bucket_partition;
 void partition_release(BucketPartition *p, bool object);      // bucketed.hip
 size_t evict_idle_partitions();                               // ... the storage of every partition no object stands on goes back to the
                                                               // allocator (set_evict_hook(), ek_internal.h); bytes given back
+int partition_refine(BucketPartition *p);                     // bucket_refine.hip: decides ONCE per partition whether it gets a refined stream
+                                                              // and builds it (not under capture); "none" is an answer, not an error
 
 struct Bucketed {
     int type = 0, index_type = 0, op = 0;
@@ -691,6 +702,7 @@ struct Bucketed {
     Bucketed *owner = nullptr;             // a slice of a split table: pair_idx / x_b / u_b / m_b are the owner's page pool (not owned)
     bool meta_borrowed = false;            // ... whose counter block and glist_part are parts of ONE allocation of the caller (PagedSlice::meta)
     BucketPartition *part = nullptr;       // meta / pair_idx / x_b / page_lists and the views into them are the partition's (a reference held)
+    bool stands_on_kept = false;           // ... which was there before this object (ek_hip_bucketed_pair_create_on): a hit of its caller's cache
 
     bool has_mask = false;
     // (with or without a mask array: lanes whose index points outside the table are dropped by the partition too, and count like

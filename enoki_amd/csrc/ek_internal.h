@@ -35,6 +35,8 @@ struct Tuning {
     int early_adjoint = 1;        // EK_BUCKETED_HINT_ADJOINT is honoured (half-size buckets, adjoint sums formed in the forward pass)
     int partition_cache = 1;      // a bucket partition may be kept by its caller and stood on again (ek_hip_bucketed_partition_retain /
                                   // ek_hip_bucketed_pair_create_on); 0: both answer EK_ERR_UNSUPPORTED, every object partitions for itself
+    int partition_refine = 1;     // a kept partition gets a refined stream (entry order, groups of four: ek_refine.h) at its first hit:
+                                  // 0 never, 1 when the lookups per entry make it pay, 2 whenever the shape is covered (tests)
     int xcd_balance = 0;          // 1: the page partition deals its tiles to the workgroup classes w % 8 by fed-back weights (ek_paged.h);
                                   // 2: equal chunks, but the classes' loop durations are recorded (ek_hip_partition_class_state)
 };

@@ -167,7 +167,7 @@ EK_API int ek_hip_graph_end(ek_hip_graph **out);
 EK_API int ek_hip_graph_launch(ek_hip_graph *graph);
 EK_API uint64_t ek_hip_graph_launch_count(const ek_hip_graph *graph);   /* kernel launches inside one replay */
 EK_API int ek_hip_graph_destroy(ek_hip_graph *graph);
-EK_API int ek_hip_set_tuning(const char *key, int value);   /* "reduce_blocks_per_cu", "scatter_add_binned", "deterministic", "gather_records", "bucket_ordered", "early_adjoint", "partition_cache" */
+EK_API int ek_hip_set_tuning(const char *key, int value);   /* "reduce_blocks_per_cu", "scatter_add_binned", "deterministic", "gather_records", "bucket_ordered", "early_adjoint", "partition_cache", "partition_refine" (0 never, 1 automatic, 2 whenever the shape is covered) */
 /* Per-kernel timing: between begin and end one HIP event is recorded on the library stream after every
    launch.  ek_hip_profile_end() synchronizes and returns a malloc'd JSON array (caller free()s) of
    {"kernel", "launches", "total_ms", "bytes", "elements"}; `bytes` are the ALGORITHMIC bytes of the
