@@ -48,7 +48,7 @@ EXPORTS = [
     "ek_hip_dist_reduce_scatter", "ek_hip_dist_all_gather", "ek_hip_dist_finalize", "ek_hip_dist_rccl_path",
     "ek_hip_bucketed_applicable", "ek_hip_bucketed_pair_create", "ek_hip_bucketed_pair_create_hinted", "ek_hip_bucketed_pair_create_masked", "ek_hip_bucketed_pair_create_scalar", "ek_hip_bucketed_pair_create_scalar_device", "ek_hip_bucketed_addend_adjoint", "ek_hip_bucketed_reduce", "ek_hip_bucketed_scatter_add", "ek_hip_bucketed_scatter_add_scaled", "ek_hip_bucketed_early_pair",
     "ek_hip_bucketed_piece_counts", "ek_hip_bucketed_destroy", "ek_hip_bucketed_partition_retain", "ek_hip_bucket_partition_release", "ek_hip_bucketed_pair_create_on", "ek_hip_index_partition_create", "ek_hip_index_partition_get", "ek_hip_index_partition_destroy", "ek_hip_gather_address",
-    "ek_hip_search_sorted", "ek_hip_search_sorted_plan",
+    "ek_hip_search_sorted", "ek_hip_search_sorted_plan", "ek_hip_search_sorted_blocks", "ek_hip_search_sorted_blocks_plan",
     "ek_hip_reduce_blocks", "ek_hip_reduce_blocks_plan", "ek_hip_repeat",
     "ek_hip_psum_blocks", "ek_hip_psum_blocks_plan",
 ]
@@ -512,6 +512,32 @@ def search_sorted_plan(dtype, K):
     r, s, g = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     check(lib.ek_hip_search_sorted_plan(NP2EK[np.dtype(dtype)], ctypes.c_size_t(K), ctypes.byref(r), ctypes.byref(s), ctypes.byref(g)))
     return r.value, s.value, g.value
+
+
+def search_sorted_blocks(table, needles, block, right=False, rows=None, out=None):
+    """per needle the number of entries of ITS row of `block` table entries before it (right: not after it), uint32
+    (ek_hip_search_sorted_blocks).  rows None: needle e belongs to row e // (needles.n // R); else to row min(rows[e], R - 1)"""
+    block = int(block)
+    if out is None:
+        out = Buf(np.uint32, needles.n)
+    check(lib.ek_hip_search_sorted_blocks(table.ek, ctypes.c_void_p(out.ptr if needles.n else None),
+                                          ctypes.c_void_p(table.ptr if table.n else None),
+                                          ctypes.c_size_t(table.n // block if block else 0), ctypes.c_size_t(block),
+                                          ctypes.c_void_p(needles.ptr if needles.n else None), ctypes.c_size_t(needles.n),
+                                          ctypes.c_void_p(rows.ptr) if rows is not None else None, int(bool(right))))
+    return out
+
+
+BLOCK_SEARCH_ROUTES = {0: "none", 1: "tile", 2: "sampled", 3: "indexed-lds", 4: "indexed-global", 5: "one-row"}
+
+
+def search_sorted_blocks_plan(dtype, rows, block, n, indexed=False, compute_units=0):
+    """(route, rows_per_tile, workgroups_per_row, resident, stride, global_steps): what ek_hip_search_sorted_blocks does for `rows`
+    rows of `block` entries of `dtype` and n needles (host only).  route: a key of BLOCK_SEARCH_ROUTES"""
+    v = [ctypes.c_int() for _ in range(6)]
+    check(lib.ek_hip_search_sorted_blocks_plan(NP2EK[np.dtype(dtype)], ctypes.c_size_t(rows), ctypes.c_size_t(block), ctypes.c_size_t(n),
+                                               int(bool(indexed)), int(compute_units), *[ctypes.byref(x) for x in v]))
+    return tuple(x.value for x in v)
 
 
 def reduce_blocks(op, a, block):

@@ -19,89 +19,9 @@
 //     span sample boundaries need no special case.
 //   * 64 KiB per workgroup: two workgroups (16 waves) fit the 160 KiB of a CU, and every halving of R would add a global step --
 //     those, one request per lane and step, are what bounds large tables.
-#include "ek_map.h"
+#include "ek_search.h"
 
 namespace ek {
-
-constexpr int kSearchBlock = 512;
-constexpr int kSearchLane = 4;                    // needles per lane and item
-constexpr size_t kSearchLdsBytes = 64 * 1024;
-constexpr int kSearchBlocksPerCu = 2;
-
-struct SearchPlan {
-    uint32_t resident;      // entries or samples in LDS
-    uint32_t stride;        // sample s is entry (s + 1) * stride - 1; 1: the table is resident whole
-    uint32_t lds_top;       // first step of the LDS search: the largest power of two <= resident (0: empty table)
-    uint32_t global_steps;  // log2(stride)
-};
-
-static SearchPlan search_plan(size_t elem_size, size_t K) {
-    const size_t R = kSearchLdsBytes / elem_size;
-    SearchPlan p = { 0, 1, 0, 0 };
-    while (K / p.stride > R) { p.stride <<= 1; p.global_steps++; }
-    p.resident = (uint32_t) (K / p.stride);
-    if (p.resident) {
-        p.lds_top = 1;
-        while (p.lds_top <= p.resident / 2) p.lds_top <<= 1;
-    }
-    return p;
-}
-
-template <typename T, bool Right> __device__ __forceinline__ bool search_before(T t, T v) {
-    if constexpr (Right) return t <= v; else return t < v;
-}
-
-/// the N needles of one item: 16-byte non-temporal loads, or element loads for a pointer that is only element-aligned
-template <typename T, int N> __device__ __forceinline__ void search_load(const T *__restrict__ src, int vec, T (&v)[N]) {
-    if (vec) {
-        constexpr int V = 16 / sizeof(T);
-#pragma unroll
-        for (int j = 0; j < N / V; ++j) {
-            const Pack<T, V> pk = pack_load<T, V, true>(src + j * V);
-#pragma unroll
-            for (int k = 0; k < V; ++k) v[j * V + k] = pk.v[k];
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < N; ++k) v[k] = __builtin_nontemporal_load(src + k);
-    }
-}
-
-/// N independent searches in lockstep
-template <typename T, bool Right, int N>
-__device__ __forceinline__ void search_run(const T *lds, const T *__restrict__ table, uint32_t K, const SearchPlan &p,
-                                           const T (&v)[N], uint32_t (&result)[N]) {
-    uint32_t pos[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) pos[k] = 0;
-    for (uint32_t h = p.lds_top; h; h >>= 1) {
-        T t[N];
-#pragma unroll
-        for (int k = 0; k < N; ++k) t[k] = lds[min(pos[k] + h - 1, p.resident - 1)];
-#pragma unroll
-        for (int k = 0; k < N; ++k) pos[k] += (pos[k] + h - 1 < p.resident && search_before<T, Right>(t[k], v[k])) ? h : 0u;
-    }
-    if (p.stride > 1) {                                            // (uniform) K > R >= 1 here
-        uint32_t lo[N], len[N];
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            lo[k] = pos[k] * p.stride;                             // <= resident * stride <= K
-            len[k] = min(p.stride - 1, K - lo[k]);
-            pos[k] = 0;
-        }
-        for (uint32_t h = p.stride >> 1; h; h >>= 1) {
-            T t[N];
-#pragma unroll
-            for (int k = 0; k < N; ++k) t[k] = table[min(lo[k] + pos[k] + h - 1, K - 1)];
-#pragma unroll
-            for (int k = 0; k < N; ++k) pos[k] += (pos[k] + h - 1 < len[k] && search_before<T, Right>(t[k], v[k])) ? h : 0u;
-        }
-#pragma unroll
-        for (int k = 0; k < N; ++k) pos[k] += lo[k];
-    }
-#pragma unroll
-    for (int k = 0; k < N; ++k) result[k] = pos[k];
-}
 
 template <typename T, bool Right>
 __global__ __launch_bounds__(kSearchBlock) void k_search_sorted(uint32_t *__restrict__ out, const T *__restrict__ table, uint32_t K,
@@ -111,6 +31,7 @@ __global__ __launch_bounds__(kSearchBlock) void k_search_sorted(uint32_t *__rest
     __shared__ T lds[kSearchLdsBytes / sizeof(T)];
     for (uint32_t i = threadIdx.x; i < p.resident; i += kSearchBlock) lds[i] = table[i * p.stride + (p.stride - 1)];
     __syncthreads();
+    const uint32_t base[N] = { }, base1[1] = { };                  // the one table starts at lds[0]
 
     // (requesting a lane's NEXT item before the current one is searched changed no shape of tools/probe_search_sorted.py by more than
     //  2 % in one call on one box, at 4 to 8 more VGPRs: left out)
@@ -120,7 +41,7 @@ __global__ __launch_bounds__(kSearchBlock) void k_search_sorted(uint32_t *__rest
         T v[N];
         search_load<T, N>(needles + e, needles_vec, v);
         Pack<uint32_t, N> r;
-        search_run<T, Right, N>(lds, table, K, p, v, r.v);
+        search_run<T, Right, N>(lds, base, table, K, p, v, r.v);
         pack_store<uint32_t, N, true>(out + e, r);
     }
 
@@ -130,7 +51,7 @@ __global__ __launch_bounds__(kSearchBlock) void k_search_sorted(uint32_t *__rest
         const size_t e = threadIdx.x < peel ? threadIdx.x : peel + items * N + (threadIdx.x - peel);
         const T v[1] = { needles[e] };
         uint32_t r[1];
-        search_run<T, Right, 1>(lds, table, K, p, v, r);
+        search_run<T, Right, 1>(lds, base1, table, K, p, v, r);
         out[e] = r[0];
     }
 }
@@ -154,15 +75,6 @@ static int search_sorted(uint32_t *out, const void *table, size_t K, const void 
         hipLaunchKernelGGL((k_search_sorted<T, false>), dim3((unsigned) blocks), dim3(kSearchBlock), 0, c.stream, out, (const T *) table,
                            (uint32_t) K, (const T *) needles, n, p, (uint32_t) peel, needles_vec);
     EK_LAUNCH_CHECK("search_sorted", n, n * (sizeof(T) + sizeof(uint32_t)));
-    return EK_OK;
-}
-
-static int search_type_check(const char *what, int type, size_t K) {
-    switch (type) {
-        case EK_I32: case EK_U32: case EK_I64: case EK_U64: case EK_F32: case EK_F64: break;
-        default: return fail(EK_ERR_UNSUPPORTED, "%s: unsupported type %d", what, type);
-    }
-    if (K > 0xFFFFFFFFull) return fail(EK_ERR_UNSUPPORTED, "%s: tables of 2^32 entries or more are unsupported (%zu)", what, K);
     return EK_OK;
 }
 

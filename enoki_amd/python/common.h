@@ -245,6 +245,12 @@ template <typename Array> py::class_<Array> bind_array(py::module_ &m, const cha
         // loop over gather(table, min(i, K - 1)) < needles in one kernel
         m.def("search_sorted", [](const Array &table, const Array &needles, bool right) { return search_sorted(table, needles, right); },
               "table"_a, "needles"_a, "right"_a = false);
+        // ... with one sorted row of `block` entries per needle: the row-local count.  rows=None: len(needles) / R consecutive
+        // needles per row; rows: a UInt32 array, one row per needle, clamped to R - 1
+        m.def("block_search_sorted", [](const Array &table, const Array &needles, size_t block, bool right,
+                                        const std::optional<uint32_array_t<Array>> &rows) {
+                  return rows ? block_search_sorted(table, needles, *rows, block, right) : block_search_sorted(table, needles, block, right);
+              }, "table"_a, "needles"_a, "block"_a, "right"_a = false, "rows"_a = py::none());
         // one value per block of `block` consecutive entries (len(array) a multiple of block), and the transpose: every entry
         // `block` times in a row (numpy.repeat); block_sum and repeat are differentiable
         m.def("block_sum", [](const Array &a, size_t block) { return block_sum(a, block); }, "array"_a, "block"_a);

@@ -1643,6 +1643,31 @@ inline Index search_sorted(const Table &table, const Needles &needles, bool righ
     else return Index(table.search_sorted_(Table(needles), right));
 }
 
+/// The same search with one sorted row per needle: `table` is R rows of `block` consecutive entries, each sorted ascending (the
+/// per-row CDFs of block_psum, one spline per object), and the result is the row-local count of entries of the needle's row before
+/// it (`right`: not after it), 0 .. block.  Without `rows`, size(needles) is a multiple of R and needle e belongs to row
+/// e / (size(needles) / R) -- M samples per ray; with `rows`, needle e belongs to row min(rows[e], R - 1).  What
+/// binary_search(0, block, [&](Index i) { return gather<T>(table, row * block + min(i, block - 1)) < needles; }) returns, in one
+/// kernel and without the `row` array.  No gradient, no tape node.
+template <typename Table, typename Needles, typename Index = uint32_array_t<Table>>
+inline Index block_search_sorted(const Table &table, const Needles &needles, size_t block, bool right = false) {
+    static_assert(array_depth_v<Table> == 1, "block_search_sorted(): the table is a flat array");
+    static_assert(std::is_same_v<Table, Needles> || std::is_same_v<Needles, scalar_t<Table>>,
+                  "block_search_sorted(): table and needles must have the same element type");
+    if constexpr (std::is_same_v<Table, Needles>) return Index(table.block_search_sorted_(needles, block, right));
+    else return Index(table.block_search_sorted_(Table(needles), block, right));
+}
+template <typename Table, typename Needles, typename Rows, typename Index = uint32_array_t<Table>,
+          std::enable_if_t<array_depth_v<Rows> == 1, int> = 0>
+inline Index block_search_sorted(const Table &table, const Needles &needles, const Rows &rows, size_t block, bool right = false) {
+    static_assert(array_depth_v<Table> == 1, "block_search_sorted(): the table is a flat array");
+    static_assert(std::is_same_v<Table, Needles> || std::is_same_v<Needles, scalar_t<Table>>,
+                  "block_search_sorted(): table and needles must have the same element type");
+    static_assert(std::is_same_v<Rows, Index>, "block_search_sorted(): the rows are a UInt32 array");
+    if constexpr (std::is_same_v<Table, Needles>) return Index(table.block_search_sorted_(needles, block, right, &rows));
+    else return Index(table.block_search_sorted_(Table(needles), block, right, &rows));
+}
+
 /// One value per block of `block` consecutive entries of a flat array (the spp samples of a pixel, a row of a row-major matrix):
 /// block_sum(x, B)[j] = x[j * B] + .. + x[(j + 1) * B - 1], likewise block_prod / block_min / block_max; size(x) is a multiple of B.
 /// repeat(x, B)[i] = x[i / B] is the transpose of block_sum (numpy.repeat).  One kernel each, no index array; block_sum and repeat

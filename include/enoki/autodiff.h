@@ -817,6 +817,13 @@ template <typename Type_> struct DiffArray : ArrayTag {
         return ReplaceScalar<uint32_t>(m_value.search_sorted_(needles.m_value, right));
     }
 
+    /// ... and so is a position in the needle's own row of `block` entries (`rows`: one row per needle, itself without gradient)
+    ReplaceScalar<uint32_t> block_search_sorted_(const DiffArray &needles, size_t block, bool right,
+                                                 const ReplaceScalar<uint32_t> *rows = nullptr) const {
+        if (!rows) return ReplaceScalar<uint32_t>(m_value.block_search_sorted_(needles.m_value, block, right));
+        return ReplaceScalar<uint32_t>(m_value.block_search_sorted_(needles.m_value, block, right, &rows->value_()));
+    }
+
     // -----------------------------------------------------------------------------------------
     //  Initializers (forwarded), storage access
     // -----------------------------------------------------------------------------------------

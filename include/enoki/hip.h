@@ -1752,6 +1752,33 @@ template <typename Value_> struct HIPArray : ArrayTag {
         return r;
     }
 
+    /// Per needle the number of entries of ITS sorted row of `block` entries of this array before it (`right`: not after it), a
+    /// row-local value, in one launch (ek_hip_search_sorted_blocks).  `rows` absent: size(needles) is a multiple of the R rows and
+    /// needle e belongs to row e / (size(needles) / R), so a host-scalar needle is only accepted for R == 1; `rows` given: one row
+    /// per needle, clamped to R - 1.  Unevaluated operands are evaluated once.
+    HIPArray<uint32_t> block_search_sorted_(const HIPArray &needles, size_t block, bool right,
+                                            const HIPArray<uint32_t> *rows = nullptr) const {
+        static_assert(!IsMask, "block_search_sorted_(): not defined for masks");
+        const size_t k = size(), n = needles.size();
+        if (block == 0 || k % block != 0)
+            throw std::runtime_error("HIPArray::block_search_sorted_(): " + std::to_string(k) + " entries are no whole number of rows of " +
+                                     std::to_string(block));
+        const size_t r = k / block;
+        if (rows ? rows->size() != n : (r ? n % r != 0 : n != 0))
+            throw std::runtime_error("HIPArray::block_search_sorted_(): " + std::to_string(n) + " needles do not match " +
+                                     (rows ? std::to_string(rows->size()) + " row indices" : std::to_string(r) + " rows"));
+        if (r == 0 && n != 0) throw std::runtime_error("HIPArray::block_search_sorted_(): needles and no row to search");
+        if (n == 0) return HIPArray<uint32_t>();
+        needles.materialize();
+        if (rows) rows->materialize();
+        materialize();
+        HIPArray<uint32_t> result = HIPArray<uint32_t>::empty_(n);
+        detail::hip_check(ek_hip_search_sorted_blocks(Type, (uint32_t *) result.m_buf->ptr, ptr_(), r, block, needles.ptr_(), n,
+                                                      rows ? (const uint32_t *) rows->ptr_() : nullptr, right ? 1 : 0),
+                          "block_search_sorted_");
+        return result;
+    }
+
     /// One value per block of `block` consecutive entries: out[j] = op over [j * block, (j + 1) * block) (ek_hip_reduce_blocks;
     /// op: EK_HSUM .. EK_HMAX).  An unevaluated operand is evaluated once; a host scalar is an array of one entry.
     HIPArray block_reduce_(int op, size_t block) const {

@@ -556,6 +556,28 @@ EK_API int ek_hip_psum(int type, void *out, const void *in, size_t n);
  * split for a type and K: *resident entries or samples in LDS, *stride (1: resident whole), *global_steps per needle. */
 EK_API int ek_hip_search_sorted(int type, uint32_t *out, const void *table, size_t K, const void *needles, size_t n, int right);
 EK_API int ek_hip_search_sorted_plan(int type, size_t K, int *resident, int *stride, int *global_steps);
+/* The same search with one sorted row per needle: `table` holds `rows` rows of `block` consecutive entries, each sorted ascending
+ * and free of NaN (the rows need not be ordered against each other), and out[e] = the number of entries t of needle e's row with
+ * t < needles[e] (right != 0: t <= needles[e]), a row-local value in 0 .. block -- the per-row CDFs that ek_hip_psum_blocks writes,
+ * one spline per object.  row_index == NULL (blocked needles): n is a multiple of `rows` and needle e belongs to row
+ * e / (n / rows), "M samples per ray".  Otherwise needle e belongs to row min(row_index[e], rows - 1): the clamp is part of the
+ * contract, no row value reads outside the table.  What binary_search(0, block, [&](i) { return gather(T, row * block +
+ * min(i, block - 1)) < v; }) returns, bit for bit and from run to run, in ONE launch, without the `row` array; types, comparisons and
+ * NaN needles as for ek_hip_search_sorted.  block == 0, n % rows != 0 for blocked needles, rows == 0 with n > 0, a null pointer with
+ * n > 0: EK_ERR_INVALID; other types and rows * block >= 2^32: EK_ERR_UNSUPPORTED; n == 0: nothing is launched.  The pointers need
+ * only element alignment.  No scratch, no read-back, no host wait: capturable.
+ * ek_hip_search_sorted_blocks_plan (host only, no device access; indexed != 0: with a row_index; compute_units == 0: 256) reports the
+ * route -- *route 0 nothing to do; 1 tile of rows (blocked, a row fits 64 KiB of LDS: a workgroup stages *rows_per_tile consecutive
+ * rows with 16-byte loads and searches their needles in LDS; with few rows of many needles *workgroups_per_row > 1 workgroups stage
+ * the same row and take a piece of its needles each); 2 sampled row (blocked, larger rows: per row the two-level search of
+ * ek_hip_search_sorted, *workgroups_per_row as before); 3 indexed, the whole table staged in LDS; 4 indexed, every step in global
+ * memory (saves launches and index traffic, not bandwidth); 5 blocked with rows == 1: forwarded to ek_hip_search_sorted -- and the
+ * search inside a row: *resident entries or samples in LDS (route 4: read in global memory instead), *stride (1: the row is resident
+ * whole), *global_steps per needle after the resident ones.  A sampled row with few needles per workgroup stages fewer samples. */
+EK_API int ek_hip_search_sorted_blocks(int type, uint32_t *out, const void *table, size_t rows, size_t block, const void *needles,
+                                       size_t n, const uint32_t *row_index, int right);
+EK_API int ek_hip_search_sorted_blocks_plan(int type, size_t rows, size_t block, size_t n, int indexed, int compute_units, int *route,
+                                            int *rows_per_tile, int *workgroups_per_row, int *resident, int *stride, int *global_steps);
 /* Block reductions: out[j] = reduce_op(in[j * block .. (j + 1) * block)) for j < n / block -- the samples of a pixel summed into
  * the image, the rows of a row-major matrix -- without the index array of scatter_add(zero(n / block), x, arange(n) / block).
  * op: EK_HSUM / EK_HPROD / EK_HMIN / EK_HMAX with the semantics of ek_hip_reduce (integer sums and products wrap; floating point
