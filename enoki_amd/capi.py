@@ -51,6 +51,7 @@ EXPORTS = [
     "ek_hip_search_sorted", "ek_hip_search_sorted_plan", "ek_hip_search_sorted_blocks", "ek_hip_search_sorted_blocks_plan",
     "ek_hip_reduce_blocks", "ek_hip_reduce_blocks_plan", "ek_hip_repeat",
     "ek_hip_psum_blocks", "ek_hip_psum_blocks_plan",
+    "ek_hip_sort_blocks", "ek_hip_sort_blocks_plan",
 ]
 
 
@@ -589,6 +590,35 @@ def psum_blocks_plan(dtype, n, block, compute_units=0):
     check(lib.ek_hip_psum_blocks_plan(NP2EK[np.dtype(dtype)], ctypes.c_size_t(n), ctypes.c_size_t(block), int(compute_units),
                                       ctypes.byref(r), ctypes.byref(s), ctypes.byref(w)))
     return r.value, s.value, w.value
+
+
+SORT_DESCENDING, SORT_FLAT_INDEX = 1, 2
+BLOCK_SORT_ROUTES = {0: "trivial", 1: "packed", 2: "row", 3: "chunks+merges"}
+
+
+def sort_blocks(a, block, descending=False, flat=False, values=True, index=True, out_values=None, out_index=None):
+    """stable sort of every block of `block` entries of `a` (ek_hip_sort_blocks): returns (values, index), None for an output that
+    was not asked for.  index: uint32, the row-local position of the entry at each slot, its flat position with `flat`.
+    out_values / out_index: write into these arrays (they must not overlap `a` or each other)"""
+    if values and out_values is None:
+        out_values = Buf(a.dtype, a.n)
+    if index and out_index is None:
+        out_index = Buf(np.uint32, a.n)
+    flags = (SORT_DESCENDING if descending else 0) | (SORT_FLAT_INDEX if flat else 0)
+    check(lib.ek_hip_sort_blocks(a.ek, ctypes.c_void_p(out_values.ptr if out_values is not None else None),
+                                 ctypes.c_void_p(out_index.ptr if out_index is not None else None),
+                                 ctypes.c_void_p(a.ptr if a.n else None), ctypes.c_size_t(a.n), ctypes.c_size_t(int(block)), flags))
+    return out_values, out_index
+
+
+def sort_blocks_plan(dtype, n, block, want_index=True, compute_units=0):
+    """(route, tile_rows, chunk, merge_passes, workgroups): what ek_hip_sort_blocks does for n entries of `dtype` in blocks of
+    `block` (host only).  route: a key of BLOCK_SORT_ROUTES"""
+    r, mp = ctypes.c_int(), ctypes.c_int()
+    t, c, w = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+    check(lib.ek_hip_sort_blocks_plan(NP2EK[np.dtype(dtype)], ctypes.c_size_t(n), ctypes.c_size_t(block), int(bool(want_index)),
+                                      int(compute_units), ctypes.byref(r), ctypes.byref(t), ctypes.byref(c), ctypes.byref(mp), ctypes.byref(w)))
+    return r.value, t.value, c.value, mp.value, w.value
 
 
 class Bucketed:

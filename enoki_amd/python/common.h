@@ -262,6 +262,16 @@ template <typename Array> py::class_<Array> bind_array(py::module_ &m, const cha
         // block's end with reverse); differentiable
         m.def("block_psum", [](const Array &a, size_t block, bool exclusive, bool reverse) { return block_psum(a, block, exclusive, reverse); },
               "array"_a, "block"_a, "exclusive"_a = false, "reverse"_a = false);
+        // stable sort inside every block; block_sort is differentiable, block_argsort returns UInt32 and has no gradient
+        m.def("block_sort", [](const Array &a, size_t block, bool descending) { return block_sort(a, block, descending); },
+              "array"_a, "block"_a, "descending"_a = false,
+              "Stable sort inside every block of `block` consecutive entries (len(array) a multiple of block): ascending by <, with "
+              "descending by >; equal entries keep their input order, -0.0 == +0.0, every NaN comes last.  Per row the order of "
+              "numpy.argsort(row, kind='stable').  Differentiable.");
+        m.def("block_argsort", [](const Array &a, size_t block, bool descending, bool flat) { return block_argsort(a, block, descending, flat); },
+              "array"_a, "block"_a, "descending"_a = false, "flat"_a = false,
+              "The permutation of block_sort as UInt32: per output slot the row-local position 0 .. block - 1 of the entry that lands "
+              "there; with flat=True its position in the flat array (row * block + local), ready for gather(other, p).  No gradient.");
     }
 
     if constexpr (IsFloat) {

@@ -600,6 +600,41 @@ template <typename Value> auto Tape<Value>::append_block_psum(Index source, size
     return target;
 }
 
+// block_sort: out = gather(source, p) with the flat permutation p that the sorting call wrote along with the values.  Forward gathers
+// the source's gradient through p; backward scatters the node's gradient to p into zeros -- p is a permutation, every target is
+// written exactly once: no add, nothing order-dependent.  A size-1 gradient is a broadcast seed and is widened first, as in
+// BlockPrefixSum.
+namespace detail {
+    template <typename TapeT, typename Value> struct BlockSort : TapeT::Special {
+        typename TapeT::Offset perm;
+        explicit BlockSort(const typename TapeT::Offset &perm) : perm(perm) { }
+        void forward(typename TapeT::Detail *detail, typename TapeT::Index target, const typename TapeT::Edge &edge) const override {
+            auto &s = detail->node(edge.source);
+            Value g = s.grad;
+            if (g.size() == 1 && s.size != 1) set_slices(g, s.size);
+            TapeT::Detail::accumulate(detail->node(target).grad, gather<Value>(g, perm));
+        }
+        void backward(typename TapeT::Detail *detail, typename TapeT::Index target, const typename TapeT::Edge &edge) const override {
+            auto &t = detail->node(target);
+            Value g = t.grad;
+            if (g.size() == 1 && t.size != 1) set_slices(g, t.size);
+            Value result = zero<Value>(t.size);
+            scatter(result, g, perm);
+            TapeT::Detail::accumulate(detail->node(edge.source).grad, result);
+        }
+    };
+}
+
+template <typename Value> auto Tape<Value>::append_block_sort(Index source, const Offset &flat_perm) -> Index {
+    if (source == 0) return 0;
+    const size_t size = d->node(source).size;
+    if (flat_perm.size() != size) throw std::runtime_error("Tape::append_block_sort(): the permutation does not have the source's size");
+    Index target = append_node(size, "block_sort");
+    d->node(target).edges.emplace_back(source, new detail::BlockSort<Tape, Value>(flat_perm));
+    inc_ref_int(source, target);
+    return target;
+}
+
 // ---------------------------------------------------------------------------------------------
 //  Reference counting (autodiff.cpp:681-774)
 // ---------------------------------------------------------------------------------------------

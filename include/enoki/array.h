@@ -1703,6 +1703,33 @@ template <typename T> inline T block_psum(const T &x, size_t block, bool exclusi
     else throw std::runtime_error("block_psum(): not available for this array type");
 }
 
+/// Stable sort inside every block of `block` consecutive entries of a flat array (size(x) is a multiple of block): ascending by
+/// `<`, with `descending` by `>`; entries that compare equal keep their input order, -0.0 == +0.0 (each keeps its bits), every NaN
+/// comes after all numbers in both directions -- per row numpy.argsort(row, kind="stable").  block_sort returns the values: a
+/// ray's hits in depth order, block_sort(block_psum(w, B), B) a CDF whose rows do ascend.  block_argsort returns the permutation as
+/// a UInt32 array: the row-local position 0 .. block - 1 of the entry at each slot, or with `flat` its position in the flat array,
+/// so that gather(other, block_argsort(t, B, false, true)) reorders another array along.  One call each, no index array,
+/// bit-identical from run to run; block_sort is differentiable (its adjoint is a scatter through the permutation), block_argsort
+/// has no gradient.  An array type without the members throws.
+namespace detail {
+    template <typename T, typename = void> struct has_block_sort : std::false_type { };
+    template <typename T> struct has_block_sort<T, std::void_t<decltype(std::declval<const T &>().block_sort_(size_t(1), false))>>
+        : std::true_type { };
+    template <typename T, typename = void> struct has_block_argsort : std::false_type { };
+    template <typename T> struct has_block_argsort<T, std::void_t<decltype(std::declval<const T &>().block_argsort_(size_t(1), false, false))>>
+        : std::true_type { };
+}
+template <typename T> inline T block_sort(const T &x, size_t block, bool descending = false) {
+    static_assert(array_depth_v<T> == 1, "block_sort(): takes a flat array");
+    if constexpr (detail::has_block_sort<T>::value) return x.block_sort_(block, descending);
+    else throw std::runtime_error("block_sort(): not available for this array type");
+}
+template <typename T> inline auto block_argsort(const T &x, size_t block, bool descending = false, bool flat = false) {
+    static_assert(array_depth_v<T> == 1, "block_argsort(): takes a flat array");
+    if constexpr (detail::has_block_argsort<T>::value) return uint32_array_t<T>(x.block_argsort_(block, descending, flat));
+    else throw std::runtime_error("block_argsort(): not available for this array type");
+}
+
 /// Angle between two unit vectors / between a unit vector and the z axis, well behaved near 0 and pi (array_math.h:1404-1436)
 template <typename T> inline auto unit_angle(const T &a, const T &b) {
     auto dot_uv = dot(a, b);

@@ -130,6 +130,8 @@ template <typename Type> struct Tape {
     Index append_repeat(Index source, size_t block);
     /// block_psum(source, block, exclusive, reverse): prefix sums inside every block; its adjoint is the same scan from the other end
     Index append_block_psum(Index source, size_t block, bool exclusive, bool reverse);
+    /// block_sort(source, ..) = gather(source, flat_perm), flat_perm a permutation of 0 .. size - 1: its adjoint is a plain scatter
+    Index append_block_sort(Index source, const Offset &flat_perm);
     void set_scatter_gather_operand(Index *index, size_t size, bool permute);
 
     // ---- reference counting (ext = held by DiffArray handles, int = held by graph edges) ----
@@ -795,6 +797,24 @@ template <typename Type_> struct DiffArray : ArrayTag {
             if (m_index) idx = tape()->append_block_psum(m_index, block, exclusive, reverse);
         }
         return create(idx, std::move(result));
+    }
+
+    /// Stable sort inside every block: a tracked source asks the one sorting call for the flat permutation as well and records one
+    /// tape node that keeps it (Tape::append_block_sort); an untracked source sorts values only
+    DiffArray block_sort_(size_t block, bool descending) const {
+        if constexpr (Enabled && detail::has_block_sort<Type>::value) {
+            if (m_index) {
+                uint32_array_t<Type> perm;
+                Type result = m_value.block_sort_(block, descending, &perm);
+                return create(tape()->append_block_sort(m_index, perm), std::move(result));
+            }
+        }
+        return create(0, block_sort(m_value, block, descending));
+    }
+
+    /// The permutation is piecewise constant in the entries: computed on the detached values, no node, no edges
+    ReplaceScalar<uint32_t> block_argsort_(size_t block, bool descending, bool flat) const {
+        return ReplaceScalar<uint32_t>(block_argsort(m_value, block, descending, flat));
     }
 
     DiffArray block_prod_(size_t block) const {

@@ -1833,6 +1833,47 @@ template <typename Value_> struct HIPArray : ArrayTag {
         return r;
     }
 
+    /// Stable sort inside every block of `block` consecutive entries (ek_hip_sort_blocks): ascending by `<`, by `>` with
+    /// `descending`; equal entries keep their input order, -0.0 == +0.0, every NaN comes last; the entries' own bits.  With
+    /// `flat_perm` the same call also writes the permutation as positions in the flat array: result == gather(*this, *flat_perm).
+    /// An unevaluated operand is evaluated once; a host scalar is an array of one entry.
+    HIPArray block_sort_(size_t block, bool descending, HIPArray<uint32_t> *flat_perm = nullptr) const {
+        HIPArray values;
+        sort_blocks_("block_sort_", block, (descending ? EK_SORT_DESCENDING : 0) | EK_SORT_FLAT_INDEX, &values, flat_perm);
+        return values;
+    }
+
+    /// ... and the permutation alone: per output slot the row-local position 0 .. block - 1 of the entry that lands there, or with
+    /// `flat` its position in the flat array (row * block + local), ready for gather(other, p).  No values are written.
+    HIPArray<uint32_t> block_argsort_(size_t block, bool descending, bool flat) const {
+        HIPArray<uint32_t> index;
+        sort_blocks_("block_argsort_", block, (descending ? EK_SORT_DESCENDING : 0) | (flat ? EK_SORT_FLAT_INDEX : 0), nullptr, &index);
+        return index;
+    }
+
+private:
+    /// one ek_hip_sort_blocks call for the outputs asked for; the checks come before the operand is evaluated and before any call
+    void sort_blocks_(const char *who, size_t block, int flags, HIPArray *values, HIPArray<uint32_t> *index) const {
+        static_assert(!IsMask, "block_sort_(): not defined for masks");
+        const size_t n = size();
+        if (block == 0 || n % block != 0)
+            throw std::runtime_error("HIPArray::" + std::string(who) + "(): " + std::to_string(n) + " entries are no whole number of blocks of " +
+                                     std::to_string(block));
+        if (n > 0xFFFFFFFFull)
+            throw std::runtime_error("HIPArray::" + std::string(who) + "(): " + std::to_string(n) + " entries, more than 2^32 - 1, are not supported");
+        if (!&ek_hip_sort_blocks)
+            throw std::runtime_error("HIPArray::" + std::string(who) + "(): this C ABI has no entry ek_hip_sort_blocks");
+        if (values) *values = HIPArray();
+        if (index) *index = HIPArray<uint32_t>();
+        if (n == 0) return;
+        materialize();
+        if (values) *values = empty_(n);
+        if (index) *index = HIPArray<uint32_t>::empty_(n);
+        detail::hip_check(ek_hip_sort_blocks(Type, values ? values->m_buf->ptr : nullptr, index ? (uint32_t *) index->m_buf->ptr : nullptr,
+                                             ptr_(), n, block, flags), who);
+    }
+public:
+
     // -----------------------------------------------------------------------------------------
     //  Storage access
     // -----------------------------------------------------------------------------------------

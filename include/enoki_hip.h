@@ -624,6 +624,34 @@ EK_API EK_OPTIONAL int ek_hip_repeat(int type, void *out, const void *in, size_t
 enum { EK_SCAN_EXCLUSIVE = 1, EK_SCAN_REVERSE = 2 };
 EK_API EK_OPTIONAL int ek_hip_psum_blocks(int type, void *out, const void *in, size_t n, size_t block, int flags);
 EK_API EK_OPTIONAL int ek_hip_psum_blocks_plan(int type, size_t n, size_t block, int compute_units, int *regime, int *splits, size_t *workgroups);
+/* Stable sort inside every block: for row j < n / block, with x = in + j * block and p the permutation that puts x in order,
+ *     out_index[j * block + k]  = p[k]  (the row-local position 0 .. block - 1 of the entry that lands at slot k;
+ *                                        + j * block with EK_SORT_FLAT_INDEX: ready for a gather from another array)
+ *     out_values[j * block + k] = x[p[k]], the entry's own bits
+ * -- a ray's hits in depth order, a row of prefix sums made ascending for ek_hip_search_sorted_blocks, old and new samples merged.
+ * Order: ascending by `<`; entries that compare equal keep their input order (stable); -0.0 and +0.0 compare equal and keep their
+ * bits; every NaN, whatever its sign bit or payload, comes after all numbers, in input order.  EK_SORT_DESCENDING orders by `>`,
+ * ties still in input order, NaN still last.  Per row this is numpy.argsort(row, kind="stable"), descending
+ * numpy.argsort(-row, kind="stable") for floating point and numpy.argsort(~row, kind="stable") for integers, exactly.
+ * Either output pointer may be NULL (not both): that output is neither computed into memory nor needs a buffer.  I32 .. F64
+ * (EK_BOOL or an unknown type: EK_ERR_UNSUPPORTED); n > 2^32 - 1: EK_ERR_UNSUPPORTED.  block == 0, n % block != 0, both outputs
+ * NULL, a null `in` with n > 0, an unknown flag bit, or `in` and the outputs (or the two outputs) overlapping: EK_ERR_INVALID;
+ * n == 0: nothing is launched.  The pointers need only element alignment.  Guarantees:
+ *   - the order is total on (key, input position), so the result is a function of the input alone: bit-identical from run to run;
+ *   - no atomics, no read-back, no host wait: capturable into a step graph; scratch comes from ek_hip_malloc and is freed
+ *     stream-ordered;
+ *   - no kernel waits for another workgroup: what one workgroup needs from another is a later launch on the stream.
+ * ek_hip_sort_blocks_plan (host only, no device access; want_index and compute_units change no route today) reports *route:
+ * 0 trivial (block == 1: copy / zeros / 0, 1, 2, ..), 1 packed (block <= 2048: *tile_rows whole rows per workgroup, padded to a
+ * power of two and sorted at once by a bitonic network in LDS), 2 one workgroup per row (block <= *chunk: 8192 entries for 4-byte
+ * types, 4096 for 8-byte types), 3 chunks and merges (longer rows: chunks of *chunk entries sorted to scratch, then
+ * *merge_passes = ceil(log2(ceil(block / chunk))) merge launches, the last of which writes the caller's outputs: 1 + *merge_passes
+ * launches in all), and *workgroups, the grid of its first launch.  EK_OPTIONAL as above. */
+#define EK_SORT_DESCENDING 1
+#define EK_SORT_FLAT_INDEX 2
+EK_API EK_OPTIONAL int ek_hip_sort_blocks(int type, void *out_values, uint32_t *out_index, const void *in, size_t n, size_t block, int flags);
+EK_API EK_OPTIONAL int ek_hip_sort_blocks_plan(int type, size_t n, size_t block, int want_index, int compute_units, int *route,
+                                               size_t *tile_rows, size_t *chunk, int *merge_passes, size_t *workgroups);
 
 /* Stable sort of (key, element number) pairs by the low `key_bits` bits of 32-bit keys:
  *     keys_out = keys sorted ascending, perm_out[j] = original position of keys_out[j]; equal keys keep their order.
