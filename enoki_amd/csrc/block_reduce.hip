@@ -22,19 +22,14 @@
 //   4 split   fewer than 2 x #CU blocks of at least 16 Ki entries: every block is cut into S pieces of P entries (P a multiple of the
 //             vector width: the pieces of a block share its alignment) so that about 4 x #CU workgroups run; the same kernel as 3
 //             writes m x S partials, which the packed kernel folds with B = S.  Two launches in a fixed order.
+// The kernel of 3 and 4 (k_reduce_segments), the tile and split rules (tile_blocks, split_shape) and head_of are shared with the
+// other per-block primitives: ek_block.h.  The staging of 2 stays spelled out in k_reduce_packed, k_scan_packed and k_sort_packed:
+// as a function of its own it compiles to other code for the 8-byte types.
 // No atomics, no read-back, no host wait; the partials of 4 come from the caching allocator (capturable).  Every sum has a fixed
 // shape for a given (type, op, n, B, alignment, #CU): run-to-run identical.
-#include "ek_reduce.h"
-
-#include <algorithm>
+#include "ek_block.h"
 
 namespace ek {
-
-constexpr size_t kPackedTileBytes = 16 * 1024;
-constexpr size_t kPackedMaxBlock = 1024;          // entries: at least one vector width of blocks per tile for 4- and 8-byte types
-constexpr size_t kSplitMinPiece = 8192;           // entries
-constexpr size_t kSplitMaxPieces = kPackedMaxBlock;
-constexpr size_t kMaxGrid = 0x7FFFFFFFull;
 
 struct BlockPlan {
     int regime;
@@ -44,11 +39,9 @@ struct BlockPlan {
 };
 
 static void packed_shape(size_t elem, size_t m, size_t B, BlockPlan &p) {
-    const size_t N = 16 / elem, E = kPackedTileBytes / elem;
-    p.tile_blocks = (uint32_t) std::max<size_t>(N, E / B / N * N);
+    p.tile_blocks = tile_blocks(elem, m, B, p.workgroups);
     p.glog = 0;
     while ((1u << p.glog) < B && p.glog < 6) p.glog++;
-    p.workgroups = std::min<size_t>((m + p.tile_blocks - 1) / p.tile_blocks, kMaxGrid);
 }
 
 static BlockPlan block_plan(size_t elem, size_t n, size_t B, int num_cu) {
@@ -61,34 +54,20 @@ static BlockPlan block_plan(size_t elem, size_t n, size_t B, int num_cu) {
         p.workgroups = std::min<size_t>(std::min<size_t>((((n / N + 3) / 4 + 1) + 255) / 256, cu * 4), 2048);
         return p;
     }
-    if (B <= kPackedMaxBlock) {
+    if (B <= kBlockPackedMax) {
         p.regime = 2;
         packed_shape(elem, m, B, p);
         return p;
     }
-    p.regime = 3;
-    if (m < 2 * cu) {
-        size_t S = std::min(std::min((4 * cu + m - 1) / m, B / kSplitMinPiece), kSplitMaxPieces);
-        if (S >= 2) {
-            p.piece = ((B + S - 1) / S + N - 1) / N * N;
-            p.splits = (B + p.piece - 1) / p.piece;        // (every piece holds at least one entry)
-            if (p.splits >= 2) p.regime = 4;
-            else { p.splits = 1; p.piece = B; }
-        }
-    }
-    p.workgroups = std::min<size_t>(m * p.splits, kMaxGrid);
+    p.regime = split_shape(elem, m, B, cu, p.splits, p.piece) ? 4 : 3;
+    p.workgroups = std::min<size_t>(m * p.splits, kBlockMaxGrid);
     return p;
-}
-
-/// entries of `p` in front of its first 16-byte boundary (p is a multiple of sizeof(T))
-template <typename T> __device__ __forceinline__ uint32_t head_of(const T *p) {
-    return (uint32_t) (((16u - (uint32_t) (reinterpret_cast<uintptr_t>(p) & 15u)) & 15u) / sizeof(T));
 }
 
 template <typename R, typename T>
 __global__ __launch_bounds__(256) void k_reduce_packed(T *__restrict__ out, const T *__restrict__ in, size_t m, uint32_t B, uint32_t tile_blocks,
                                                        uint32_t glog, size_t tiles) {
-    constexpr uint32_t N = 16 / sizeof(T), E = kPackedTileBytes / sizeof(T);
+    constexpr uint32_t N = 16 / sizeof(T), E = kBlockTileBytes / sizeof(T);
     __shared__ __attribute__((aligned(16))) T tile[E + N];
     const uint32_t G = 1u << glog, group = threadIdx.x >> glog, l = threadIdx.x & (G - 1), groups = 256u >> glog;
     for (size_t t = blockIdx.x; t < tiles; t += gridDim.x) {
@@ -119,45 +98,6 @@ __global__ __launch_bounds__(256) void k_reduce_packed(T *__restrict__ out, cons
             if (l == 0 && blk < nb) out[b0 + blk] = acc;
         }
         __syncthreads();
-    }
-}
-
-/// segment = piece s of block j (S pieces of `piece` entries per block; S == 1: the whole block), one workgroup each
-template <typename R, typename T>
-__global__ __launch_bounds__(256) void k_reduce_segments(T *__restrict__ out, const T *__restrict__ in, size_t B, size_t piece, uint32_t S,
-                                                         size_t segments) {
-    constexpr uint32_t N = 16 / sizeof(T), U = 4;
-    for (size_t seg = blockIdx.x; seg < segments; seg += gridDim.x) {
-        size_t j = seg, off = 0;
-        if (S > 1) { j = seg / S; off = (seg - j * S) * piece; }
-        const size_t len = B - off < piece ? B - off : piece;
-        const T *src = in + j * B + off;
-        size_t head = head_of(src);
-        if (head > len) head = len;
-        const size_t nvec = (len - head) / N, tail = len - head - nvec * N;
-        const T *vsrc = src + head;
-        T acc[U];
-#pragma unroll
-        for (uint32_t k = 0; k < U; ++k) acc[k] = R::identity();
-        for (size_t v0 = threadIdx.x; v0 < nvec; v0 += 256 * U) {
-            Pack<T, N> p[U];
-#pragma unroll
-            for (uint32_t k = 0; k < U; ++k)
-                if (v0 + k * 256 < nvec) p[k] = pack_load<T, N, true>(vsrc + (v0 + k * 256) * N);
-#pragma unroll
-            for (uint32_t k = 0; k < U; ++k) {
-                if (v0 + k * 256 < nvec) {
-#pragma unroll
-                    for (uint32_t i = 0; i < N; ++i) acc[k] = R::combine(acc[k], p[k].v[i]);
-                }
-            }
-        }
-        if (threadIdx.x < head) acc[0] = R::combine(acc[0], src[threadIdx.x]);
-        if (threadIdx.x < tail) acc[1] = R::combine(acc[1], vsrc[nvec * N + threadIdx.x]);
-        T v = R::combine(R::combine(acc[0], acc[1]), R::combine(acc[2], acc[3]));
-        v = block_reduce<R>(v);
-        if (threadIdx.x == 0) out[seg] = v;
-        __syncthreads();                                  // (block_reduce's LDS words are written again by the next segment)
     }
 }
 
@@ -244,7 +184,7 @@ template <typename T> static int repeat_typed(void *out, const void *in, size_t 
     Context &c = ctx();
     constexpr size_t N = 16 / sizeof(T);
     const size_t total = m * B;
-    size_t peel = ((16 - (reinterpret_cast<uintptr_t>(out) & 15u)) & 15u) / sizeof(T);
+    size_t peel = head_of((const T *) out);
     if (peel > total) peel = total;
     const size_t items = (total - peel) / N;
     size_t blocks = (items + 255) / 256, cap = (size_t) c.num_cu * 16;
@@ -257,13 +197,6 @@ template <typename T> static int repeat_typed(void *out, const void *in, size_t 
     return EK_OK;
 }
 
-static int block_type_check(const char *what, int type) {
-    switch (type) {
-        case EK_I32: case EK_U32: case EK_I64: case EK_U64: case EK_F32: case EK_F64: return EK_OK;
-        default: return fail(EK_ERR_UNSUPPORTED, "%s: unsupported type %d", what, type);
-    }
-}
-
 } // namespace ek
 
 using namespace ek;
@@ -271,9 +204,8 @@ using namespace ek;
 extern "C" {
 
 int ek_hip_reduce_blocks_plan(int type, size_t n, size_t block, int compute_units, int *regime, int *splits, size_t *workgroups) {
-    if (int rc = block_type_check("ek_hip_reduce_blocks_plan()", type)) return rc;
-    if (block == 0 || n % block != 0)
-        return fail(EK_ERR_INVALID, "ek_hip_reduce_blocks_plan(): %zu entries are no whole number of blocks of %zu", n, block);
+    if (int rc = numeric_type_check("ek_hip_reduce_blocks_plan()", type)) return rc;
+    if (int rc = blocks_shape_check("ek_hip_reduce_blocks_plan()", n, block)) return rc;
     if (compute_units < 0) return fail(EK_ERR_INVALID, "ek_hip_reduce_blocks_plan(): %d compute units", compute_units);
     BlockPlan p = { 0, 1, block, 0, 0, 0 };
     if (n) p = block_plan(type_size(type), n, block, compute_units);
@@ -286,36 +218,24 @@ int ek_hip_reduce_blocks_plan(int type, size_t n, size_t block, int compute_unit
 int ek_hip_reduce_blocks(int op, int type, void *out, const void *in, size_t n, size_t block) {
     if (int rc = ensure_init()) return rc;
     if (op < 0 || op >= EK_REDUCE_COUNT) return fail(EK_ERR_INVALID, "ek_hip_reduce_blocks(): unknown op %d", op);
-    if (int rc = block_type_check("ek_hip_reduce_blocks()", type)) return rc;
-    if (block == 0 || n % block != 0)
-        return fail(EK_ERR_INVALID, "ek_hip_reduce_blocks(): %zu entries are no whole number of blocks of %zu", n, block);
+    if (int rc = numeric_type_check("ek_hip_reduce_blocks()", type)) return rc;
+    if (int rc = blocks_shape_check("ek_hip_reduce_blocks()", n, block)) return rc;
     if (n == 0) return EK_OK;
     const size_t elem = type_size(type);
-    if (!out || !in) return fail(EK_ERR_INVALID, "ek_hip_reduce_blocks(): null pointer");
-    if ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(in)) & (elem - 1))
-        return fail(EK_ERR_INVALID, "ek_hip_reduce_blocks(): pointer not aligned to the element size");
+    if (int rc = pointers_check("ek_hip_reduce_blocks()", elem, out, in)) return rc;
     const BlockPlan p = block_plan(elem, n, block, ctx().num_cu);
     if (p.regime == 0) return ek_hip_memcpy_device(out, in, n * elem);
     if (p.regime == 1) return ek_hip_reduce(op, type, out, in, n);
-    switch (type) {
-        case EK_I32: return reduce_blocks_typed<int32_t>(op, out, in, n, block, p);
-        case EK_U32: return reduce_blocks_typed<uint32_t>(op, out, in, n, block, p);
-        case EK_I64: return reduce_blocks_typed<int64_t>(op, out, in, n, block, p);
-        case EK_U64: return reduce_blocks_typed<uint64_t>(op, out, in, n, block, p);
-        case EK_F32: return reduce_blocks_typed<float>(op, out, in, n, block, p);
-        default: return reduce_blocks_typed<double>(op, out, in, n, block, p);
-    }
+    return dispatch_numeric(type, [&](auto t) { return reduce_blocks_typed<typename decltype(t)::type>(op, out, in, n, block, p); });
 }
 
 int ek_hip_repeat(int type, void *out, const void *in, size_t m, size_t block) {
     if (int rc = ensure_init()) return rc;
-    if (int rc = block_type_check("ek_hip_repeat()", type)) return rc;
+    if (int rc = numeric_type_check("ek_hip_repeat()", type)) return rc;
     if (block == 0) return fail(EK_ERR_INVALID, "ek_hip_repeat(): blocks of 0 entries");
     if (m == 0) return EK_OK;
     const size_t elem = type_size(type);
-    if (!out || !in) return fail(EK_ERR_INVALID, "ek_hip_repeat(): null pointer");
-    if ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(in)) & (elem - 1))
-        return fail(EK_ERR_INVALID, "ek_hip_repeat(): pointer not aligned to the element size");
+    if (int rc = pointers_check("ek_hip_repeat()", elem, out, in)) return rc;
     if (block == 1) return ek_hip_memcpy_device(out, in, m * elem);
     return elem == 4 ? repeat_typed<uint32_t>(out, in, m, block) : repeat_typed<uint64_t>(out, in, m, block);
 }

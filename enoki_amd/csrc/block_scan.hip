@@ -37,21 +37,14 @@
 //                        reverses every vector in registers.  EXCLUSIVE hands every lane its left neighbour's last running sum
 //                        through LDS.  Stores are 16-byte stores where `out` shares the alignment of `in`, by element otherwise.
 //   3 split              fewer than 2 x #CU blocks of at least 16 Ki entries: (1) the totals of S pieces per block (multiples of the
-//                        vector width, the last may be shorter), (2) the packed kernel, exclusive, same direction, over the m x S
+//                        vector width, the last may be shorter; split_shape and k_reduce_segments of ek_block.h), (2) the packed kernel, exclusive, same direction, over the m x S
 //                        totals with B = S, (3) the chunk kernel over every piece with its carry-in; for EXCLUSIVE (4) a seam launch
 //                        that writes every piece's first entry: the last running sum of the piece before it, bit for bit.  12 bytes
 //                        per 4-byte entry instead of 8.  Scratch from ek_hip_malloc, freed stream-ordered.
-#include "ek_reduce.h"
-
-#include <algorithm>
+#include "ek_block.h"
 
 namespace ek {
 
-constexpr size_t kScanTileBytes = 16 * 1024;
-constexpr size_t kScanPackedMaxBlock = 1024;       // entries: one vector width of blocks fits a tile for 4- and 8-byte types
-constexpr size_t kScanSplitMinPiece = 8192;        // entries: a block is split only from 16 Ki entries up
-constexpr size_t kScanSplitMaxPieces = kScanPackedMaxBlock;
-constexpr size_t kScanMaxGrid = 0x7FFFFFFFull;
 constexpr int kScanBlockRows = 4;                  // a chunk: 256 lanes x 16 bytes x 4 rows = 16 KiB
 
 struct ScanPlan {
@@ -61,35 +54,24 @@ struct ScanPlan {
     size_t workgroups;                   // grid of the first launch
 };
 
-static void scan_packed_shape(size_t elem, size_t m, size_t B, ScanPlan &p) {
-    const size_t N = 16 / elem, E = kScanTileBytes / elem;
-    p.tile_blocks = (uint32_t) std::max<size_t>(N, E / B / N * N);
+static void packed_shape(size_t elem, size_t m, size_t B, ScanPlan &p) {
+    p.tile_blocks = tile_blocks(elem, m, B, p.workgroups);
     p.glog = 0;
     while ((4u << p.glog) < B && p.glog < 6) p.glog++;
     p.run = (uint32_t) ((B + (1u << p.glog) - 1) >> p.glog) | 1u;
-    p.workgroups = std::min<size_t>((m + p.tile_blocks - 1) / p.tile_blocks, kScanMaxGrid);
 }
 
 static ScanPlan scan_plan(size_t elem, size_t n, size_t B, int num_cu) {
     ScanPlan p = { 0, 1, B, 0, 0, 0, 1 };
-    const size_t m = n / B, N = 16 / elem, cu = num_cu > 0 ? (size_t) num_cu : 256;
+    const size_t m = n / B, cu = num_cu > 0 ? (size_t) num_cu : 256;
     if (B == 1) return p;
-    if (B <= kScanPackedMaxBlock) {
+    if (B <= kBlockPackedMax) {
         p.regime = 1;
-        scan_packed_shape(elem, m, B, p);
+        packed_shape(elem, m, B, p);
         return p;
     }
-    p.regime = 2;
-    if (m < 2 * cu) {
-        size_t S = std::min(std::min((4 * cu + m - 1) / m, B / kScanSplitMinPiece), kScanSplitMaxPieces);
-        if (S >= 2) {
-            p.piece = ((B + S - 1) / S + N - 1) / N * N;
-            p.splits = (B + p.piece - 1) / p.piece;        // (every piece holds at least one entry)
-            if (p.splits >= 2) p.regime = 3;
-            else { p.splits = 1; p.piece = B; }
-        }
-    }
-    p.workgroups = std::min<size_t>(m * p.splits, kScanMaxGrid);
+    p.regime = split_shape(elem, m, B, cu, p.splits, p.piece) ? 3 : 2;
+    p.workgroups = std::min<size_t>(m * p.splits, kBlockMaxGrid);
     return p;
 }
 
@@ -111,16 +93,11 @@ template <typename T> __device__ __forceinline__ T block_scan_shfl_up(T v, int d
     }
 }
 
-/// entries of `p` in front of its first 16-byte boundary (p is a multiple of sizeof(T))
-template <typename T> __device__ __forceinline__ uint32_t scan_head_of(const T *p) {
-    return (uint32_t) (((16u - (uint32_t) (reinterpret_cast<uintptr_t>(p) & 15u)) & 15u) / sizeof(T));
-}
-
 // ---- route 1: packed ---------------------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void k_scan_packed(T *out, const T *in, size_t m, uint32_t B, uint32_t tile_blocks, uint32_t glog,
                                                      uint32_t run, size_t tiles, int flags) {
-    constexpr uint32_t N = 16 / sizeof(T), E = kScanTileBytes / sizeof(T);
+    constexpr uint32_t N = 16 / sizeof(T), E = kBlockTileBytes / sizeof(T);
     constexpr T kId = sum_identity<T>;
     __shared__ __attribute__((aligned(16))) T tile_in[E + N];
     __shared__ __attribute__((aligned(16))) T tile_out[E + N];
@@ -132,7 +109,7 @@ __global__ __launch_bounds__(256) void k_scan_packed(T *out, const T *in, size_t
         const size_t b0 = t * tile_blocks;
         const uint32_t nb = (uint32_t) (m - b0 < tile_blocks ? m - b0 : tile_blocks), len = nb * B;       // len <= E
         const T *src = in + b0 * B;
-        uint32_t head = scan_head_of(src);
+        uint32_t head = head_of(src);
         if (head > len) head = len;
         // element e of the tile lives at tile_in[shift + e]: the first whole vector lands on a 16-byte boundary of LDS
         const uint32_t shift = (N - head) % N, nvec = (len - head) / N, tail = len - head - nvec * N;
@@ -144,7 +121,7 @@ __global__ __launch_bounds__(256) void k_scan_packed(T *out, const T *in, size_t
         if (threadIdx.x < tail) ti[head + nvec * N + threadIdx.x] = src[head + nvec * N + threadIdx.x];
         // ... and element e of the result at tile_out[oshift + e], by the alignment of `out`
         T *dst = out + b0 * B;
-        uint32_t ohead = scan_head_of(dst);
+        uint32_t ohead = head_of(dst);
         if (ohead > len) ohead = len;
         const uint32_t oshift = (N - ohead) % N, onvec = (len - ohead) / N, otail = len - ohead - onvec * N;
         T *to = tile_out + oshift;
@@ -208,7 +185,7 @@ __global__ __launch_bounds__(256) void k_scan_segments(T *out, const T *in, size
         const T *src = in + j * B + off;
         T *dst = out + j * B + off;
         const bool first = S == 1 || (rev ? s == S - 1 : s == 0);          // the piece the scan of this block starts with
-        size_t head = scan_head_of(src);
+        size_t head = head_of(src);
         if (head > len) head = len;
         const size_t nvec = (len - head) / V;
         const uint32_t tail = (uint32_t) (len - head - nvec * V);
@@ -347,45 +324,6 @@ __global__ __launch_bounds__(256) void k_scan_segments(T *out, const T *in, size
     }
 }
 
-/// route 3, launch 1: the total of every piece (the shape of k_reduce_segments: four accumulators per lane, the 256-thread fold)
-template <typename T>
-__global__ __launch_bounds__(256) void k_scan_totals(T *__restrict__ totals, const T *__restrict__ in, size_t B, size_t piece, uint32_t S,
-                                                     size_t segments) {
-    using Rd = Reducer<EK_HSUM, T>;
-    constexpr uint32_t N = 16 / sizeof(T), U = 4;
-    for (size_t seg = blockIdx.x; seg < segments; seg += gridDim.x) {
-        const size_t j = seg / S, off = (seg - j * S) * piece;
-        const size_t len = B - off < piece ? B - off : piece;
-        const T *src = in + j * B + off;
-        size_t head = scan_head_of(src);
-        if (head > len) head = len;
-        const size_t nvec = (len - head) / N, tail = len - head - nvec * N;
-        const T *vsrc = src + head;
-        T acc[U];
-#pragma unroll
-        for (uint32_t k = 0; k < U; ++k) acc[k] = Rd::identity();
-        for (size_t v0 = threadIdx.x; v0 < nvec; v0 += 256 * U) {
-            Pack<T, N> p[U];
-#pragma unroll
-            for (uint32_t k = 0; k < U; ++k)
-                if (v0 + k * 256 < nvec) p[k] = pack_load<T, N, true>(vsrc + (v0 + k * 256) * N);
-#pragma unroll
-            for (uint32_t k = 0; k < U; ++k) {
-                if (v0 + k * 256 < nvec) {
-#pragma unroll
-                    for (uint32_t i = 0; i < N; ++i) acc[k] = Rd::combine(acc[k], p[k].v[i]);
-                }
-            }
-        }
-        if (threadIdx.x < head) acc[0] = Rd::combine(acc[0], src[threadIdx.x]);
-        if (threadIdx.x < tail) acc[1] = Rd::combine(acc[1], vsrc[nvec * N + threadIdx.x]);
-        T v = Rd::combine(Rd::combine(acc[0], acc[1]), Rd::combine(acc[2], acc[3]));
-        v = block_reduce<Rd>(v);
-        if (threadIdx.x == 0) totals[seg] = v;
-        __syncthreads();                                  // (block_reduce's LDS words are written again by the next segment)
-    }
-}
-
 /// route 3, launch 4 (EXCLUSIVE only): the first entry of every piece but the one its block's scan starts with is the last running
 /// sum of the piece in front of it
 template <typename T>
@@ -414,11 +352,12 @@ template <typename T> static int scan_split(T *out, const T *in, size_t n, size_
     Context &c = ctx();
     const size_t m = n / B, segments = m * p.splits;
     T *carries = scratch, *lasts = (flags & EK_SCAN_EXCLUSIVE) ? scratch + segments : nullptr;
-    hipLaunchKernelGGL((k_scan_totals<T>), dim3((unsigned) p.workgroups), dim3(256), 0, c.stream, carries, in, B, p.piece, (uint32_t) p.splits,
-                       segments);
+    // launch 1: the total of every piece, by the kernel that sums the pieces of block_sum (ek_block.h)
+    hipLaunchKernelGGL((k_reduce_segments<Reducer<EK_HSUM, T>, T>), dim3((unsigned) p.workgroups), dim3(256), 0, c.stream, carries, in, B, p.piece,
+                       (uint32_t) p.splits, segments);
     EK_LAUNCH_CHECK("psum_blocks_totals", n, (n + segments) * sizeof(T));
     ScanPlan fold = p;
-    scan_packed_shape(sizeof(T), m, p.splits, fold);
+    packed_shape(sizeof(T), m, p.splits, fold);
     if (int rc = launch_scan_packed<T>("psum_blocks_carries", carries, carries, m, p.splits, fold, (flags & EK_SCAN_REVERSE) | EK_SCAN_EXCLUSIVE))
         return rc;
     hipLaunchKernelGGL((k_scan_segments<T>), dim3((unsigned) p.workgroups), dim3(256), 0, c.stream, out, in, B, p.piece, (uint32_t) p.splits,
@@ -451,13 +390,6 @@ template <typename T> static int psum_blocks_typed(void *out_, const void *in_, 
     return rc;
 }
 
-static int scan_type_check(const char *what, int type) {
-    switch (type) {
-        case EK_I32: case EK_U32: case EK_I64: case EK_U64: case EK_F32: case EK_F64: return EK_OK;
-        default: return fail(EK_ERR_UNSUPPORTED, "%s: unsupported type %d", what, type);
-    }
-}
-
 } // namespace ek
 
 using namespace ek;
@@ -465,9 +397,8 @@ using namespace ek;
 extern "C" {
 
 int ek_hip_psum_blocks_plan(int type, size_t n, size_t block, int compute_units, int *regime, int *splits, size_t *workgroups) {
-    if (int rc = scan_type_check("ek_hip_psum_blocks_plan()", type)) return rc;
-    if (block == 0 || n % block != 0)
-        return fail(EK_ERR_INVALID, "ek_hip_psum_blocks_plan(): %zu entries are no whole number of blocks of %zu", n, block);
+    if (int rc = numeric_type_check("ek_hip_psum_blocks_plan()", type)) return rc;
+    if (int rc = blocks_shape_check("ek_hip_psum_blocks_plan()", n, block)) return rc;
     if (compute_units < 0) return fail(EK_ERR_INVALID, "ek_hip_psum_blocks_plan(): %d compute units", compute_units);
     ScanPlan p = { 0, 1, block, 0, 0, 0, 0 };
     if (n) p = scan_plan(type_size(type), n, block, compute_units);
@@ -479,29 +410,19 @@ int ek_hip_psum_blocks_plan(int type, size_t n, size_t block, int compute_units,
 
 int ek_hip_psum_blocks(int type, void *out, const void *in, size_t n, size_t block, int flags) {
     if (int rc = ensure_init()) return rc;
-    if (int rc = scan_type_check("ek_hip_psum_blocks()", type)) return rc;
+    if (int rc = numeric_type_check("ek_hip_psum_blocks()", type)) return rc;
     if (flags & ~(EK_SCAN_EXCLUSIVE | EK_SCAN_REVERSE)) return fail(EK_ERR_INVALID, "ek_hip_psum_blocks(): unknown flags %d", flags);
-    if (block == 0 || n % block != 0)
-        return fail(EK_ERR_INVALID, "ek_hip_psum_blocks(): %zu entries are no whole number of blocks of %zu", n, block);
+    if (int rc = blocks_shape_check("ek_hip_psum_blocks()", n, block)) return rc;
     if (n == 0) return EK_OK;
     const size_t elem = type_size(type);
-    if (!out || !in) return fail(EK_ERR_INVALID, "ek_hip_psum_blocks(): null pointer");
-    if ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(in)) & (elem - 1))
-        return fail(EK_ERR_INVALID, "ek_hip_psum_blocks(): pointer not aligned to the element size");
+    if (int rc = pointers_check("ek_hip_psum_blocks()", elem, out, in)) return rc;
     const ScanPlan p = scan_plan(elem, n, block, ctx().num_cu);
     if (p.regime == 0) {
         // one term per sum: the input itself; no term at all: +0 (all bits clear in every type)
         if (flags & EK_SCAN_EXCLUSIVE) return ek_hip_memset(out, 0, n * elem);
         return out == in ? EK_OK : ek_hip_memcpy_device(out, in, n * elem);
     }
-    switch (type) {
-        case EK_I32: return psum_blocks_typed<int32_t>(out, in, n, block, p, flags);
-        case EK_U32: return psum_blocks_typed<uint32_t>(out, in, n, block, p, flags);
-        case EK_I64: return psum_blocks_typed<int64_t>(out, in, n, block, p, flags);
-        case EK_U64: return psum_blocks_typed<uint64_t>(out, in, n, block, p, flags);
-        case EK_F32: return psum_blocks_typed<float>(out, in, n, block, p, flags);
-        default: return psum_blocks_typed<double>(out, in, n, block, p, flags);
-    }
+    return dispatch_numeric(type, [&](auto t) { return psum_blocks_typed<typename decltype(t)::type>(out, in, n, block, p, flags); });
 }
 
 }

@@ -89,7 +89,7 @@ static BlockSearchPlan block_search_plan(size_t elem_size, size_t R, size_t B, s
 /// `count` consecutive entries into LDS: 16-byte loads between an element-wise head and tail
 template <typename T> __device__ __forceinline__ void stage_entries(T *lds, const T *__restrict__ src, uint32_t count) {
     constexpr uint32_t V = 16 / sizeof(T);
-    uint32_t head = (uint32_t) (((16 - (reinterpret_cast<uintptr_t>(src) & 15u)) & 15u) / sizeof(T));
+    uint32_t head = head_of(src);
     if (head > count) head = count;
     if (threadIdx.x < head) lds[threadIdx.x] = src[threadIdx.x];
     const uint32_t vecs = (count - head) / V;
@@ -108,7 +108,7 @@ __device__ __forceinline__ void search_range(uint32_t *__restrict__ out, const T
                                              const Search &search) {
     constexpr int N = kSearchLane;
     const size_t count = e1 - e0;
-    size_t peel = ((16 - (reinterpret_cast<uintptr_t>(out + e0) & 15u)) & 15u) / sizeof(uint32_t);
+    size_t peel = head_of<size_t>(out + e0);
     if (peel > count) peel = count;
     const int vec = (reinterpret_cast<uintptr_t>(needles + e0 + peel) & 15u) == 0;
     const size_t items = (count - peel) / N;
@@ -251,7 +251,7 @@ static int block_search_sorted(uint32_t *out, const void *table_, size_t R, size
                                 B, M, p.pieces, p.jobs, p.sp);
             break;
         default: {
-            size_t peel = ((16 - (reinterpret_cast<uintptr_t>(out) & 15u)) & 15u) / sizeof(uint32_t);
+            size_t peel = head_of(out);
             if (peel > n) peel = n;
             const bool lds = p.route == kRouteIndexedLds;
             block_search_launch(lds ? (right ? k_block_search_indexed<T, true, true> : k_block_search_indexed<T, false, true>)
@@ -302,14 +302,9 @@ int ek_hip_search_sorted_blocks(int type, uint32_t *out, const void *table, size
     if (n == 0) return EK_OK;
     if (!out || !needles || !table) return fail(EK_ERR_INVALID, "ek_hip_search_sorted_blocks(): null pointer");
     if (rows == 1 && !row_index) return ek_hip_search_sorted(type, out, table, block, needles, n, right);
-    switch (type) {
-        case EK_I32: return block_search_sorted<int32_t>(out, table, rows, block, needles, n, row_index, right);
-        case EK_U32: return block_search_sorted<uint32_t>(out, table, rows, block, needles, n, row_index, right);
-        case EK_I64: return block_search_sorted<int64_t>(out, table, rows, block, needles, n, row_index, right);
-        case EK_U64: return block_search_sorted<uint64_t>(out, table, rows, block, needles, n, row_index, right);
-        case EK_F32: return block_search_sorted<float>(out, table, rows, block, needles, n, row_index, right);
-        default: return block_search_sorted<double>(out, table, rows, block, needles, n, row_index, right);
-    }
+    return dispatch_numeric(type, [&](auto t) {
+        return block_search_sorted<typename decltype(t)::type>(out, table, rows, block, needles, n, row_index, right);
+    });
 }
 
 }

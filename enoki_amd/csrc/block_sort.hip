@@ -21,13 +21,13 @@
 // sort_plan() picks the route (ek_hip_sort_blocks_plan reports it):
 //   0 trivial            B == 1: a copy for values, zeros for row-local positions, 0, 1, 2, .. for flat positions.
 //   1 packed             B <= 2048.  A workgroup of 256 lanes stages tile_rows = 2048 / P whole rows (P = B rounded up to a power
-//                        of two) in LDS with 16-byte non-temporal loads; head / shift / tail as in k_scan_packed, so a view that
+//                        of two) in LDS with 16-byte non-temporal loads; head / shift / tail as in k_reduce_packed, so a view that
 //                        starts off a 16-byte boundary costs no more.  Row r of the tile owns composite slots [r * P, (r + 1) * P).
 //                        One bitonic network runs over ALL slots at once: stage (k, j) pairs slot lo with lo | j, j < P, so a pair
 //                        never leaves its row, and the direction comes from the ROW-LOCAL slot number (lo & (P - 1)) & k, so every
 //                        row ends ascending.  log2(P) (log2(P) + 1) / 2 stages, one barrier each.  Then every lane takes its 8 result
 //                        slots into registers (value from the staged row, position), and the composite area is REUSED as the two
-//                        output tiles, which leave with 16-byte stores, each shifted for its own pointer's alignment.
+//                        output tiles, which leave with 16-byte stores (tile_out, ek_block.h), each shifted for its own pointer's alignment.
 //                        LDS: 2048 staged entries + 2048 composites: 24 KiB (4-byte types), 40 KiB (8-byte).  Rows of 1025 .. 2048
 //                        entries are a tile of one row: the same 2048-slot network takes 2.2 ms here for 64 Mi float32 entries
 //                        at B = 1025 and took 3.3 ms with the 1024 lanes of route 2.
@@ -50,9 +50,7 @@
 //                        Scratch: one or two buffers of n composites from ek_hip_malloc, freed stream-ordered.
 // Grids are capped; every kernel walks its tiles / segments in a grid-stride loop.  Positions are 32-bit (n < 2^32), global offsets
 // size_t.  An output that was not asked for is neither computed into memory nor allocated.
-#include "ek_map.h"
-
-#include <algorithm>
+#include "ek_block.h"
 
 namespace ek {
 
@@ -172,23 +170,6 @@ template <int ES> __device__ __forceinline__ void sort_bitonic(const CompStore<E
     }
 }
 
-/// entries of `p` in front of its first 16-byte boundary (p is a multiple of sizeof(T))
-template <typename T> __device__ __forceinline__ uint32_t sort_head_of(const T *p) {
-    return (uint32_t) (((16u - (uint32_t) (reinterpret_cast<uintptr_t>(p) & 15u)) & 15u) / sizeof(T));
-}
-
-/// `len` entries of the LDS tile `t` (entry e at t[e], t + head on a 16-byte boundary of LDS) to dst: 16-byte stores between the
-/// entries in front of dst's first boundary and those behind its last
-template <typename T> __device__ __forceinline__ void sort_tile_out(T *dst, const T *t, uint32_t len, uint32_t head) {
-    constexpr uint32_t N = 16 / sizeof(T);
-    const uint32_t nvec = (len - head) / N, tail = len - head - nvec * N;
-    if (threadIdx.x < head) dst[threadIdx.x] = t[threadIdx.x];
-#pragma unroll 4
-    for (uint32_t v = threadIdx.x; v < nvec; v += 256)
-        pack_store<T, N, true>(dst + head + v * N, *reinterpret_cast<const Pack<T, N> *>(t + head + v * N));
-    if (threadIdx.x < tail) dst[head + nvec * N + threadIdx.x] = t[head + nvec * N + threadIdx.x];
-}
-
 // ---- route 1: packed ---------------------------------------------------------------------------------------------------------
 template <typename U, int KIND>
 __global__ __launch_bounds__(256) void k_sort_packed(U *outv, uint32_t *outi, const U *in, size_t m, uint32_t B, uint32_t plog,
@@ -207,7 +188,7 @@ __global__ __launch_bounds__(256) void k_sort_packed(U *outv, uint32_t *outi, co
         const size_t r0 = t * tile_rows;
         const uint32_t nr = (uint32_t) (m - r0 < tile_rows ? m - r0 : tile_rows), len = nr * B;        // len <= C
         const U *src = in + r0 * B;
-        uint32_t head = sort_head_of(src);
+        uint32_t head = head_of(src);
         if (head > len) head = len;
         // entry e of the tile lives at tile_in[shift + e]: the first whole vector lands on a 16-byte boundary of LDS
         const uint32_t shift = (N - head) % N, nvec = (len - head) / N, tail = len - head - nvec * N;
@@ -217,7 +198,7 @@ __global__ __launch_bounds__(256) void k_sort_packed(U *outv, uint32_t *outi, co
         for (uint32_t v = threadIdx.x; v < nvec; v += 256)
             *reinterpret_cast<Pack<U, N> *>(ti + head + v * N) = pack_load<U, N, true>(src + head + v * N);
         if (threadIdx.x < tail) ti[head + nvec * N + threadIdx.x] = src[head + nvec * N + threadIdx.x];
-        __syncthreads();        // (also: the last tile's stores out of `area` are done)
+        __syncthreads();       // (also: the last tile's stores out of `area` are done)
         const uint32_t slots = nr << plog;
         for (uint32_t s = threadIdx.x; s < slots; s += 256) {
             const uint32_t r = s >> plog, k = s & (P - 1);
@@ -240,11 +221,11 @@ __global__ __launch_bounds__(256) void k_sort_packed(U *outv, uint32_t *outi, co
         __syncthreads();
         uint32_t vhead = 0, ihead = 0;
         if (outv) {
-            vhead = sort_head_of(outv + r0 * B);
+            vhead = head_of(outv + r0 * B);
             if (vhead > len) vhead = len;
         }
         if (outi) {
-            ihead = sort_head_of(outi + r0 * B);
+            ihead = head_of(outi + r0 * B);
             if (ihead > len) ihead = len;
         }
         U *tv = tile_v + (N - vhead) % N;
@@ -258,8 +239,8 @@ __global__ __launch_bounds__(256) void k_sort_packed(U *outv, uint32_t *outi, co
             }
         }
         __syncthreads();
-        if (outv) sort_tile_out<U>(outv + r0 * B, tv, len, vhead);
-        if (outi) sort_tile_out<uint32_t>(outi + r0 * B, tx, len, ihead);
+        if (outv) tile_out<U>(outv + r0 * B, tv, len, vhead);
+        if (outi) tile_out<uint32_t>(outi + r0 * B, tx, len, ihead);
     }
 }
 
@@ -423,15 +404,8 @@ static int sort_blocks_typed(void *outv_, uint32_t *outi, const void *in_, size_
     return rc;
 }
 
-static int sort_type_check(const char *what, int type) {
-    switch (type) {
-        case EK_I32: case EK_U32: case EK_I64: case EK_U64: case EK_F32: case EK_F64: return EK_OK;
-        default: return fail(EK_ERR_UNSUPPORTED, "%s: unsupported type %d", what, type);
-    }
-}
-
 static int sort_shape_check(const char *what, size_t n, size_t block) {
-    if (block == 0 || n % block != 0) return fail(EK_ERR_INVALID, "%s: %zu entries are no whole number of blocks of %zu", what, n, block);
+    if (int rc = blocks_shape_check(what, n, block)) return rc;
     if (n > kSortMaxEntries) return fail(EK_ERR_UNSUPPORTED, "%s: %zu entries, more than 2^32 - 1", what, n);
     return EK_OK;
 }
@@ -450,7 +424,7 @@ extern "C" {
 int ek_hip_sort_blocks_plan(int type, size_t n, size_t block, int want_index, int compute_units, int *route, size_t *tile_rows,
                             size_t *chunk, int *merge_passes, size_t *workgroups) {
     (void) want_index;          // the index travels inside the composite either way: it changes no route
-    if (int rc = sort_type_check("ek_hip_sort_blocks_plan()", type)) return rc;
+    if (int rc = numeric_type_check("ek_hip_sort_blocks_plan()", type)) return rc;
     if (int rc = sort_shape_check("ek_hip_sort_blocks_plan()", n, block)) return rc;
     if (compute_units < 0) return fail(EK_ERR_INVALID, "ek_hip_sort_blocks_plan(): %d compute units", compute_units);
     const SortPlan p = sort_plan(type_size(type), n, block);
@@ -464,15 +438,16 @@ int ek_hip_sort_blocks_plan(int type, size_t n, size_t block, int want_index, in
 
 int ek_hip_sort_blocks(int type, void *out_values, uint32_t *out_index, const void *in, size_t n, size_t block, int flags) {
     if (int rc = ensure_init()) return rc;
-    if (int rc = sort_type_check("ek_hip_sort_blocks()", type)) return rc;
+    if (int rc = numeric_type_check("ek_hip_sort_blocks()", type)) return rc;
     if (flags & ~(EK_SORT_DESCENDING | EK_SORT_FLAT_INDEX)) return fail(EK_ERR_INVALID, "ek_hip_sort_blocks(): unknown flags %d", flags);
     if (int rc = sort_shape_check("ek_hip_sort_blocks()", n, block)) return rc;
     if (!out_values && !out_index) return fail(EK_ERR_INVALID, "ek_hip_sort_blocks(): no output");
     if (n == 0) return EK_OK;
     const size_t elem = type_size(type);
-    if (!in) return fail(EK_ERR_INVALID, "ek_hip_sort_blocks(): null pointer");
-    if (((reinterpret_cast<uintptr_t>(out_values) | reinterpret_cast<uintptr_t>(in)) & (elem - 1)) || (reinterpret_cast<uintptr_t>(out_index) & 3u))
-        return fail(EK_ERR_INVALID, "ek_hip_sort_blocks(): pointer not aligned to the element size");
+    if (int rc = pointers_check("ek_hip_sort_blocks()", elem, in)) return rc;
+    // (an output that was not asked for is a null pointer: aligned)
+    if (int rc = alignment_check("ek_hip_sort_blocks()", elem, out_values)) return rc;
+    if (int rc = alignment_check("ek_hip_sort_blocks()", 4, out_index)) return rc;
     if (sort_overlap(in, n * elem, out_values, n * elem) || sort_overlap(in, n * elem, out_index, n * 4) ||
         sort_overlap(out_values, n * elem, out_index, n * 4))
         return fail(EK_ERR_INVALID, "ek_hip_sort_blocks(): in and the outputs overlap");

@@ -6,7 +6,7 @@
 // clamped to the range it searches, whatever the needle and whatever the table holds.
 #pragma once
 
-#include "ek_map.h"
+#include "ek_block.h"        // head_of, numeric_type_check, dispatch_numeric
 
 namespace ek {
 
@@ -103,10 +103,7 @@ static uint32_t search_top(size_t count) {
 }
 
 static int search_type_check(const char *what, int type, size_t K) {
-    switch (type) {
-        case EK_I32: case EK_U32: case EK_I64: case EK_U64: case EK_F32: case EK_F64: break;
-        default: return fail(EK_ERR_UNSUPPORTED, "%s: unsupported type %d", what, type);
-    }
+    if (int rc = numeric_type_check(what, type)) return rc;
     if (K > 0xFFFFFFFFull) return fail(EK_ERR_UNSUPPORTED, "%s: tables of 2^32 entries or more are unsupported (%zu)", what, K);
     return EK_OK;
 }

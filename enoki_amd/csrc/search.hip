@@ -61,7 +61,7 @@ static int search_sorted(uint32_t *out, const void *table, size_t K, const void 
     RoctxRange range("enoki-hip: search_sorted");
     Context &c = ctx();
     const SearchPlan p = search_plan(sizeof(T), K);
-    size_t peel = ((16 - (reinterpret_cast<uintptr_t>(out) & 15u)) & 15u) / sizeof(uint32_t);
+    size_t peel = head_of(out);
     if (peel > n) peel = n;
     const int needles_vec = aligned16((const T *) needles + peel);
     const size_t items = (n - peel) / kSearchLane;
