@@ -52,6 +52,7 @@ EXPORTS = [
     "ek_hip_reduce_blocks", "ek_hip_reduce_blocks_plan", "ek_hip_repeat",
     "ek_hip_psum_blocks", "ek_hip_psum_blocks_plan",
     "ek_hip_sort_blocks", "ek_hip_sort_blocks_plan",
+    "ek_hip_reduce_segments", "ek_hip_repeat_segments", "ek_hip_reduce_segments_plan",
 ]
 
 
@@ -619,6 +620,40 @@ def sort_blocks_plan(dtype, n, block, want_index=True, compute_units=0):
     check(lib.ek_hip_sort_blocks_plan(NP2EK[np.dtype(dtype)], ctypes.c_size_t(n), ctypes.c_size_t(block), int(bool(want_index)),
                                       int(compute_units), ctypes.byref(r), ctypes.byref(t), ctypes.byref(c), ctypes.byref(mp), ctypes.byref(w)))
     return r.value, t.value, c.value, mp.value, w.value
+
+
+SEGMENT_ROUTES = {0: "nothing", 1: "grouped", 2: "segment", 3: "split"}
+
+
+def reduce_segments(op, a, starts):
+    """out[j] = op over a[min(starts[j], n) : min(starts[j + 1], n)] with starts[m] := n = a.n, for the m = starts.n ragged segments
+    that the uint32 array `starts` (non-decreasing) gives (ek_hip_reduce_segments); an empty segment yields the identity"""
+    out = Buf(a.dtype, starts.n)
+    check(lib.ek_hip_reduce_segments(REDUCE[op], a.ek, ctypes.c_void_p(out.ptr), ctypes.c_void_p(a.ptr if a.n else None), ctypes.c_size_t(a.n),
+                                     ctypes.c_void_p(starts.ptr if starts.n else None), ctypes.c_size_t(starts.n)))
+    return out
+
+
+def repeat_segments(a, starts, n, out=None):
+    """out[i] = a[j] for the last j with starts[j] <= i, 0 in front of starts[0], for i < n: the transpose of the segment sum
+    (ek_hip_repeat_segments); a.n == starts.n.  `out`: write into this array of n entries"""
+    n = int(n)
+    if out is None:
+        out = Buf(a.dtype, n)
+    if a.n != starts.n:
+        raise ValueError(f"repeat_segments(): {a.n} values do not match {starts.n} starts")
+    check(lib.ek_hip_repeat_segments(a.ek, ctypes.c_void_p(out.ptr), ctypes.c_void_p(a.ptr if a.n else None),
+                                     ctypes.c_void_p(starts.ptr if starts.n else None), ctypes.c_size_t(a.n), ctypes.c_size_t(n)))
+    return out
+
+
+def reduce_segments_plan(dtype, n, m, compute_units=0):
+    """(route, group_lanes, splits, workgroups): what ek_hip_reduce_segments does for m segments of n entries of `dtype` (host only;
+    nothing but these numbers enters).  route: a key of SEGMENT_ROUTES; group_lanes: lanes per segment of the grouped route"""
+    r, g, s, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
+    check(lib.ek_hip_reduce_segments_plan(NP2EK[np.dtype(dtype)], ctypes.c_size_t(n), ctypes.c_size_t(m), int(compute_units),
+                                          ctypes.byref(r), ctypes.byref(g), ctypes.byref(s), ctypes.byref(w)))
+    return r.value, g.value, s.value, w.value
 
 
 class Bucketed:

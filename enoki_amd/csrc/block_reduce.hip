@@ -146,6 +146,12 @@ template <typename T> static int reduce_blocks_typed(int op, void *out, const vo
     }
 }
 
+int reduce_blocks_packed(int op, int type, void *out, const void *in, size_t m, size_t B) {
+    BlockPlan p = { 2, 1, B, 0, 0, 1 };
+    packed_shape(type_size(type), m, B, p);
+    return dispatch_numeric(type, [&](auto t) { return reduce_blocks_typed<typename decltype(t)::type>(op, out, in, m * B, B, p); });
+}
+
 // ---- repeat --------------------------------------------------------------------------------------------------------------
 // One 16-byte non-temporal store per lane and trip.  A lane divides ONCE (its first element / B); every later trip is `threads`
 // vectors further on: quotient and remainder advance by the host's (dq, dr) with one conditional carry.  Inside a vector the

@@ -1,8 +1,34 @@
 // What the per-block primitives share (block_reduce.hip, block_scan.hip, block_search.hip, block_sort.hip: one result per block
-// of B consecutive entries, or one per entry of every block): the handling of a pointer that is only element-aligned, the way of
-// an LDS tile out to such a pointer, the sum of a piece of a block, the rule that splits few long blocks into pieces, and the
-// argument checks.  The routes themselves are described at the top of each of the four files.
+// of B consecutive entries, or one per entry of every block; block_segments.hip: the same for ragged segments): the handling of a
+// pointer that is only element-aligned, the way of an LDS tile out to such a pointer, the sum of a piece of a block or segment,
+// the rule that splits few long blocks into pieces, the bounds of a ragged segment, and the argument checks.  The routes
+// themselves are described at the top of each of the five files.
 #pragma once
+
+#include <cstdint>
+
+// The one rule of this header that a plain host compiler can take as well (tests/cpp/segment_sum_host.cpp checks it there);
+// everything behind it needs the HIP compiler.
+#if defined(__HIPCC__)
+#  define EK_BLOCK_RULE __host__ __device__ inline __attribute__((always_inline))
+#else
+#  define EK_BLOCK_RULE inline
+#endif
+
+namespace ek {
+
+/// Ragged segments (block_segments.hip): segment j of an array of n entries is [lo, hi) with lo = min(start, n) and
+/// hi = max(lo, min(next, n)), where `start` is starts[j] and `next` is starts[j + 1] (n behind the last start).  Whatever the two
+/// values are -- above n, decreasing -- lo <= hi <= n.
+EK_BLOCK_RULE void segment_clamp(uint32_t start, uint32_t next, uint32_t n, uint32_t &lo, uint32_t &hi) {
+    lo = start < n ? start : n;
+    const uint32_t e = next < n ? next : n;
+    hi = e > lo ? e : lo;
+}
+
+} // namespace ek
+
+#if defined(__HIPCC__)
 
 #include "ek_reduce.h"
 
@@ -98,45 +124,55 @@ template <typename T> __device__ __forceinline__ void tile_out(T *dst, const T *
     if (threadIdx.x < tail) dst[head + nvec * N + threadIdx.x] = tile[head + nvec * N + threadIdx.x];
 }
 
-/// segment = piece s of block j (S pieces of `piece` entries per block; S == 1: the whole block), one workgroup each: the block is
-/// streamed as k_reduce_stage1 streams an array (16-byte non-temporal loads, four in flight per lane, four accumulators, the
-/// 256-thread fold)
+/// All 256 lanes: the reduction of the `len` entries at src (a multiple of sizeof(T)), in thread 0.  The entries are streamed as
+/// k_reduce_stage1 streams an array (16-byte non-temporal loads, four in flight per lane, four accumulators, the 256-thread fold);
+/// those in front of the first 16-byte boundary and behind the last are taken one per lane.  len == 0: the identity.
+template <typename R, typename T> __device__ __forceinline__ T reduce_piece(const T *__restrict__ src, size_t len) {
+    constexpr uint32_t N = 16 / sizeof(T), U = 4;
+    size_t head = head_of(src);
+    if (head > len) head = len;
+    const size_t nvec = (len - head) / N, tail = len - head - nvec * N;
+    const T *vsrc = src + head;
+    T acc[U];
+#pragma unroll
+    for (uint32_t k = 0; k < U; ++k) acc[k] = R::identity();
+    for (size_t v0 = threadIdx.x; v0 < nvec; v0 += 256 * U) {
+        Pack<T, N> p[U];
+#pragma unroll
+        for (uint32_t k = 0; k < U; ++k)
+            if (v0 + k * 256 < nvec) p[k] = pack_load<T, N, true>(vsrc + (v0 + k * 256) * N);
+#pragma unroll
+        for (uint32_t k = 0; k < U; ++k) {
+            if (v0 + k * 256 < nvec) {
+#pragma unroll
+                for (uint32_t i = 0; i < N; ++i) acc[k] = R::combine(acc[k], p[k].v[i]);
+            }
+        }
+    }
+    if (threadIdx.x < head) acc[0] = R::combine(acc[0], src[threadIdx.x]);
+    if (threadIdx.x < tail) acc[1] = R::combine(acc[1], vsrc[nvec * N + threadIdx.x]);
+    const T v = R::combine(R::combine(acc[0], acc[1]), R::combine(acc[2], acc[3]));
+    return block_reduce<R>(v);
+}
+
+/// segment = piece s of block j (S pieces of `piece` entries per block; S == 1: the whole block), one workgroup each
 template <typename R, typename T>
 __global__ __launch_bounds__(256) void k_reduce_segments(T *__restrict__ out, const T *__restrict__ in, size_t B, size_t piece, uint32_t S,
                                                          size_t segments) {
-    constexpr uint32_t N = 16 / sizeof(T), U = 4;
     for (size_t seg = blockIdx.x; seg < segments; seg += gridDim.x) {
         size_t j = seg, off = 0;
         if (S > 1) { j = seg / S; off = (seg - j * S) * piece; }
         const size_t len = B - off < piece ? B - off : piece;
-        const T *src = in + j * B + off;
-        size_t head = head_of(src);
-        if (head > len) head = len;
-        const size_t nvec = (len - head) / N, tail = len - head - nvec * N;
-        const T *vsrc = src + head;
-        T acc[U];
-#pragma unroll
-        for (uint32_t k = 0; k < U; ++k) acc[k] = R::identity();
-        for (size_t v0 = threadIdx.x; v0 < nvec; v0 += 256 * U) {
-            Pack<T, N> p[U];
-#pragma unroll
-            for (uint32_t k = 0; k < U; ++k)
-                if (v0 + k * 256 < nvec) p[k] = pack_load<T, N, true>(vsrc + (v0 + k * 256) * N);
-#pragma unroll
-            for (uint32_t k = 0; k < U; ++k) {
-                if (v0 + k * 256 < nvec) {
-#pragma unroll
-                    for (uint32_t i = 0; i < N; ++i) acc[k] = R::combine(acc[k], p[k].v[i]);
-                }
-            }
-        }
-        if (threadIdx.x < head) acc[0] = R::combine(acc[0], src[threadIdx.x]);
-        if (threadIdx.x < tail) acc[1] = R::combine(acc[1], vsrc[nvec * N + threadIdx.x]);
-        T v = R::combine(R::combine(acc[0], acc[1]), R::combine(acc[2], acc[3]));
-        v = block_reduce<R>(v);
+        const T v = reduce_piece<R, T>(in + j * B + off, len);
         if (threadIdx.x == 0) out[seg] = v;
         __syncthreads();                                  // (block_reduce's LDS words are written again by the next segment)
     }
 }
 
+// ---- what block_segments.hip takes from block_reduce.hip --------------------------------------------------------------------
+/// the packed block kernel over m blocks of B <= kBlockPackedMax entries: the fold of the m x B partials of a split route
+int reduce_blocks_packed(int op, int type, void *out, const void *in, size_t m, size_t B);
+
 } // namespace ek
+
+#endif // __HIPCC__

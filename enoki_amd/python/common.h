@@ -272,6 +272,26 @@ template <typename Array> py::class_<Array> bind_array(py::module_ &m, const cha
               "array"_a, "block"_a, "descending"_a = false, "flat"_a = false,
               "The permutation of block_sort as UInt32: per output slot the row-local position 0 .. block - 1 of the entry that lands "
               "there; with flat=True its position in the flat array (row * block + local), ready for gather(other, p).  No gradient.");
+        // one value per ragged segment (starts: UInt32, non-decreasing, starts[m] := len(array)), and the transpose; segment_sum
+        // and segment_repeat are differentiable, starts carries no gradient
+        using Starts = uint32_array_t<Array>;
+        m.def("segment_sum", [](const Array &a, const Starts &starts) { return segment_sum(a, starts); }, "array"_a, "starts"_a,
+              "Sum of every ragged segment of a flat array: starts is a UInt32 array of m non-decreasing positions, starts[m] := n = "
+              "len(array), and result[j] = array[min(starts[j], n)] + .. + array[min(starts[j + 1], n) - 1]; an empty segment gives 0.  "
+              "The starts of given counts are block_psum(counts, len(counts), exclusive=True).  Differentiable; the adjoint is "
+              "segment_repeat.  Bit-identical from run to run.");
+        m.def("segment_prod", [](const Array &a, const Starts &starts) { return segment_prod(a, starts); }, "array"_a, "starts"_a,
+              "Product of every ragged segment (see segment_sum); an empty segment gives 1.  No gradient.");
+        m.def("segment_min", [](const Array &a, const Starts &starts) { return segment_min(a, starts); }, "array"_a, "starts"_a,
+              "Minimum of every ragged segment (see segment_sum); floating point: minNum, NaN for an empty segment; integers: the "
+              "type's maximum for an empty segment.  No gradient.");
+        m.def("segment_max", [](const Array &a, const Starts &starts) { return segment_max(a, starts); }, "array"_a, "starts"_a,
+              "Maximum of every ragged segment (see segment_sum); floating point: maxNum, NaN for an empty segment; integers: the "
+              "type's lowest value for an empty segment.  No gradient.");
+        m.def("segment_repeat", [](const Array &v, const Starts &starts, size_t size) { return segment_repeat(v, starts, size); },
+              "values"_a, "starts"_a, "size"_a,
+              "The transpose of segment_sum over `size` entries: result[i] = values[j] for the last j with starts[j] <= i, 0 in front "
+              "of starts[0]; len(values) == len(starts).  Differentiable; the adjoint is segment_sum.");
     }
 
     if constexpr (IsFloat) {

@@ -635,6 +635,50 @@ template <typename Value> auto Tape<Value>::append_block_sort(Index source, cons
     return target;
 }
 
+// segment_sum and segment_repeat over the same `starts` are each other's transpose, so one Special serves both nodes, as
+// BlockTranspose does: `sums` says that the node is the segment sum of its source (forward reduces the source's gradient, backward
+// repeats the node's over the `flat` entries of the source); otherwise the node repeats its source and the directions swap.  The
+// node keeps `starts`, as the block_sort node keeps its permutation, and releases it with the edge; `starts` carries no gradient.
+// A size-1 gradient is a broadcast seed and is widened first.
+namespace detail {
+    template <typename TapeT, typename Value> struct SegmentTranspose : TapeT::Special {
+        typename TapeT::Offset starts;
+        size_t flat;
+        bool sums;
+        SegmentTranspose(const typename TapeT::Offset &starts, size_t flat, bool sums) : starts(starts), flat(flat), sums(sums) { }
+        Value apply(Value g, size_t size, bool reduce) const {
+            if (g.size() == 1 && size != 1) set_slices(g, size);
+            return reduce ? segment_sum(g, starts) : segment_repeat(g, starts, flat);
+        }
+        void forward(typename TapeT::Detail *detail, typename TapeT::Index target, const typename TapeT::Edge &edge) const override {
+            auto &s = detail->node(edge.source);
+            TapeT::Detail::accumulate(detail->node(target).grad, apply(s.grad, s.size, sums));
+        }
+        void backward(typename TapeT::Detail *detail, typename TapeT::Index target, const typename TapeT::Edge &edge) const override {
+            auto &t = detail->node(target);
+            TapeT::Detail::accumulate(detail->node(edge.source).grad, apply(t.grad, t.size, !sums));
+        }
+    };
+}
+
+template <typename Value> auto Tape<Value>::append_segment_sum(Index source, const Offset &starts) -> Index {
+    if (source == 0) return 0;
+    Index target = append_node(starts.size(), "segment_sum");
+    d->node(target).edges.emplace_back(source, new detail::SegmentTranspose<Tape, Value>(starts, d->node(source).size, true));
+    inc_ref_int(source, target);
+    return target;
+}
+
+template <typename Value> auto Tape<Value>::append_segment_repeat(Index source, const Offset &starts, size_t size) -> Index {
+    if (source == 0) return 0;
+    if (starts.size() != d->node(source).size)
+        throw std::runtime_error("Tape::append_segment_repeat(): the starts do not have the source's size");
+    Index target = append_node(size, "segment_repeat");
+    d->node(target).edges.emplace_back(source, new detail::SegmentTranspose<Tape, Value>(starts, size, false));
+    inc_ref_int(source, target);
+    return target;
+}
+
 // ---------------------------------------------------------------------------------------------
 //  Reference counting (autodiff.cpp:681-774)
 // ---------------------------------------------------------------------------------------------

@@ -1730,6 +1730,38 @@ template <typename T> inline auto block_argsort(const T &x, size_t block, bool d
     else throw std::runtime_error("block_argsort(): not available for this array type");
 }
 
+/// One value per RAGGED segment of a flat array: `starts` is a UInt32 array of m non-decreasing positions, starts[m] := n = size(x),
+/// and segment_sum(x, starts)[j] = x[min(starts[j], n)] + .. + x[min(starts[j + 1], n) - 1], likewise segment_prod / segment_min /
+/// segment_max; an empty segment yields +0 / 1 / NaN (the type's max / lowest for integers).  The starts of given counts are
+/// block_psum(counts, size(counts), true) -- the samples of every ray that compress() left.  segment_repeat(v, starts, n)[i] = v[j]
+/// for the last j with starts[j] <= i (0 in front of starts[0]) is the transpose of segment_sum.  No index array, bit-identical
+/// from run to run; segment_sum and segment_repeat are differentiable in both modes (`starts` carries no gradient).  An array
+/// type without these members throws at run time.
+namespace detail {
+    template <typename T, typename Starts, typename = void> struct has_segment_ops : std::false_type { };
+    template <typename T, typename Starts>
+    struct has_segment_ops<T, Starts, std::void_t<decltype(std::declval<const T &>().segment_sum_(std::declval<const Starts &>())),
+                                                  decltype(std::declval<const T &>().segment_repeat_(std::declval<const Starts &>(), size_t(1)))>>
+        : std::true_type { };
+}
+#define ENOKI_HIP_SEGMENT_OP(name)                                                                                           \
+    template <typename T, typename Starts> inline T name(const T &x, const Starts &starts) {                                 \
+        static_assert(array_depth_v<T> == 1, #name "(): takes a flat array");                                               \
+        if constexpr (detail::has_segment_ops<T, Starts>::value) {                                                                   \
+            static_assert(std::is_same_v<Starts, uint32_array_t<T>>, #name "(): the starts are a UInt32 array");             \
+            return x.name##_(starts);                                                                                        \
+        } else throw std::runtime_error(#name "(): not available for this array type");                                     \
+    }
+ENOKI_HIP_SEGMENT_OP(segment_sum) ENOKI_HIP_SEGMENT_OP(segment_prod) ENOKI_HIP_SEGMENT_OP(segment_min) ENOKI_HIP_SEGMENT_OP(segment_max)
+#undef ENOKI_HIP_SEGMENT_OP
+template <typename T, typename Starts> inline T segment_repeat(const T &v, const Starts &starts, size_t size) {
+    static_assert(array_depth_v<T> == 1, "segment_repeat(): takes a flat array");
+    if constexpr (detail::has_segment_ops<T, Starts>::value) {
+        static_assert(std::is_same_v<Starts, uint32_array_t<T>>, "segment_repeat(): the starts are a UInt32 array");
+        return v.segment_repeat_(starts, size);
+    } else throw std::runtime_error("segment_repeat(): not available for this array type");
+}
+
 /// Angle between two unit vectors / between a unit vector and the z axis, well behaved near 0 and pi (array_math.h:1404-1436)
 template <typename T> inline auto unit_angle(const T &a, const T &b) {
     auto dot_uv = dot(a, b);

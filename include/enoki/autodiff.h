@@ -132,6 +132,11 @@ template <typename Type> struct Tape {
     Index append_block_psum(Index source, size_t block, bool exclusive, bool reverse);
     /// block_sort(source, ..) = gather(source, flat_perm), flat_perm a permutation of 0 .. size - 1: its adjoint is a plain scatter
     Index append_block_sort(Index source, const Offset &flat_perm);
+    /// segment_sum(source, starts): one entry per ragged segment; its adjoint is segment_repeat() over the same starts, which the
+    /// node keeps
+    Index append_segment_sum(Index source, const Offset &starts);
+    /// segment_repeat(source, starts, size): every entry once per entry of its segment; its adjoint is segment_sum()
+    Index append_segment_repeat(Index source, const Offset &starts, size_t size);
     void set_scatter_gather_operand(Index *index, size_t size, bool permute);
 
     // ---- reference counting (ext = held by DiffArray handles, int = held by graph edges) ----
@@ -830,6 +835,41 @@ template <typename Type_> struct DiffArray : ArrayTag {
     DiffArray block_max_(size_t block) const {
         if (Enabled && m_index != 0) throw std::runtime_error("DiffArray::block_max_(): gradients not implemented");
         return create(0, block_max(m_value, block));
+    }
+
+    /// Sum of every ragged segment / every entry once per entry of its segment: each other's transpose over the same `starts`
+    /// (a UInt32 array without gradient, which the node keeps), one tape node each (Tape::append_segment_sum / append_segment_repeat)
+    DiffArray segment_sum_(const ReplaceScalar<uint32_t> &starts) const {
+        Type result = segment_sum(m_value, starts.value_());
+        Index idx = 0;
+        if constexpr (Enabled) {
+            if (m_index) idx = tape()->append_segment_sum(m_index, starts.value_());
+        }
+        return create(idx, std::move(result));
+    }
+
+    DiffArray segment_repeat_(const ReplaceScalar<uint32_t> &starts, size_t size) const {
+        Type result = segment_repeat(m_value, starts.value_(), size);
+        Index idx = 0;
+        if constexpr (Enabled) {
+            if (m_index) idx = tape()->append_segment_repeat(m_index, starts.value_(), size);
+        }
+        return create(idx, std::move(result));
+    }
+
+    DiffArray segment_prod_(const ReplaceScalar<uint32_t> &starts) const {
+        if (Enabled && m_index != 0) throw std::runtime_error("DiffArray::segment_prod_(): gradients not implemented");
+        return create(0, segment_prod(m_value, starts.value_()));
+    }
+
+    DiffArray segment_min_(const ReplaceScalar<uint32_t> &starts) const {
+        if (Enabled && m_index != 0) throw std::runtime_error("DiffArray::segment_min_(): gradients not implemented");
+        return create(0, segment_min(m_value, starts.value_()));
+    }
+
+    DiffArray segment_max_(const ReplaceScalar<uint32_t> &starts) const {
+        if (Enabled && m_index != 0) throw std::runtime_error("DiffArray::segment_max_(): gradients not implemented");
+        return create(0, segment_max(m_value, starts.value_()));
     }
 
     /// A position in a sorted table is piecewise constant in table and needles: searched on the detached values, no node, no edges

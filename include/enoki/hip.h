@@ -1814,6 +1814,51 @@ template <typename Value_> struct HIPArray : ArrayTag {
         return r;
     }
 
+    /// One value per ragged segment: with m = size(starts), starts non-decreasing and starts[m] := n = size(), out[j] = op over
+    /// [min(starts[j], n), min(starts[j + 1], n)) (ek_hip_reduce_segments; op: EK_HSUM .. EK_HMAX); an empty segment yields the
+    /// identity.  starts = block_psum(counts, size(counts), exclusive).  Unevaluated operands are evaluated once.
+    HIPArray segment_reduce_(int op, const HIPArray<uint32_t> &starts) const {
+        static_assert(!IsMask, "segment_reduce_(): not defined for masks");
+        if (!&ek_hip_reduce_segments)
+            throw std::runtime_error("HIPArray::segment_reduce_(): this C ABI has no entry ek_hip_reduce_segments");
+        const size_t n = size(), m = starts.size();
+        if (n > 0xFFFFFFFFull)
+            throw std::runtime_error("HIPArray::segment_reduce_(): " + std::to_string(n) + " entries, more than 2^32 - 1, are not supported");
+        if (m == 0) return HIPArray();
+        starts.materialize();
+        materialize();
+        HIPArray r = empty_(m);
+        detail::hip_check(ek_hip_reduce_segments(op, Type, r.m_buf->ptr, n ? ptr_() : nullptr, n, (const uint32_t *) starts.ptr_(), m),
+                          "segment_reduce_");
+        return r;
+    }
+
+    HIPArray segment_sum_(const HIPArray<uint32_t> &starts) const { return segment_reduce_(EK_HSUM, starts); }
+    HIPArray segment_prod_(const HIPArray<uint32_t> &starts) const { return segment_reduce_(EK_HPROD, starts); }
+    HIPArray segment_min_(const HIPArray<uint32_t> &starts) const { return segment_reduce_(EK_HMIN, starts); }
+    HIPArray segment_max_(const HIPArray<uint32_t> &starts) const { return segment_reduce_(EK_HMAX, starts); }
+
+    /// The transpose of the segment sum over `size` entries: out[i] = (*this)[j] for the last j with starts[j] <= i, 0 in front
+    /// of starts[0] (ek_hip_repeat_segments); size(*this) == size(starts)
+    HIPArray segment_repeat_(const HIPArray<uint32_t> &starts, size_t size) const {
+        static_assert(!IsMask, "segment_repeat_(): not defined for masks");
+        if (!&ek_hip_repeat_segments)
+            throw std::runtime_error("HIPArray::segment_repeat_(): this C ABI has no entry ek_hip_repeat_segments");
+        const size_t m = this->size();
+        if (m != starts.size())
+            throw std::runtime_error("HIPArray::segment_repeat_(): " + std::to_string(m) + " values do not match " +
+                                     std::to_string(starts.size()) + " starts");
+        if (size > 0xFFFFFFFFull)
+            throw std::runtime_error("HIPArray::segment_repeat_(): " + std::to_string(size) + " entries, more than 2^32 - 1, are not supported");
+        if (size == 0) return HIPArray();
+        starts.materialize();
+        materialize();
+        HIPArray r = empty_(size);
+        detail::hip_check(ek_hip_repeat_segments(Type, r.m_buf->ptr, m ? ptr_() : nullptr, m ? (const uint32_t *) starts.ptr_() : nullptr, m, size),
+                          "segment_repeat_");
+        return r;
+    }
+
     /// Prefix sums inside every block of `block` consecutive entries (ek_hip_psum_blocks): entry k of a block becomes the sum of
     /// its entries 0 .. k, 0 .. k - 1 with `exclusive` (the empty sum is +0), k .. block - 1 with `reverse`.  An unevaluated
     /// operand is evaluated once; a host scalar is an array of one entry.

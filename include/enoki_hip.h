@@ -652,6 +652,44 @@ EK_API EK_OPTIONAL int ek_hip_psum_blocks_plan(int type, size_t n, size_t block,
 EK_API EK_OPTIONAL int ek_hip_sort_blocks(int type, void *out_values, uint32_t *out_index, const void *in, size_t n, size_t block, int flags);
 EK_API EK_OPTIONAL int ek_hip_sort_blocks_plan(int type, size_t n, size_t block, int want_index, int compute_units, int *route,
                                                size_t *tile_rows, size_t *chunk, int *merge_passes, size_t *workgroups);
+/* Ragged segments: the counterpart of ek_hip_reduce_blocks for segments of different lengths -- the samples of a ray that are left
+ * after compress(), the hits of a ray in a mesh.  `starts` is a device array of m non-decreasing positions; with starts[m] := n,
+ * segment j is in[lo_j .. hi_j) with lo_j = min(starts[j], n) and hi_j = max(lo_j, min(starts[j + 1], n)).  Entries in front of
+ * starts[0] belong to no segment.  The starts of given counts are their exclusive prefix sum: ek_hip_psum_blocks(EK_U32, starts,
+ * counts, m, m, EK_SCAN_EXCLUSIVE).
+ *     out[j] = reduce_op(in[lo_j .. hi_j))        for j < m
+ * op: EK_HSUM / EK_HPROD / EK_HMIN / EK_HMAX with the semantics of ek_hip_reduce (integer sums and products wrap; floating point
+ * hmin / hmax are minNum / maxNum, -0 < +0); an empty segment yields the identity: +0, 1, NaN for floating point hmin / hmax
+ * (like a block of NaNs), the type's max / lowest for integer hmin / hmax.  I32 .. F64 (EK_BOOL or an unknown type:
+ * EK_ERR_UNSUPPORTED); n or m above 2^32 - 1: EK_ERR_UNSUPPORTED; an unknown op, a null `out` or `starts`, a null `in` with
+ * n > 0 or a pointer that is not element-aligned: EK_ERR_INVALID; m == 0: nothing is launched; n == 0: every entry is the identity.
+ * The pointers need only element alignment.  Guarantees:
+ *   - `starts` is never read back, so it cannot be validated; whatever it holds, no kernel reads outside in[0 .. n) and
+ *     starts[0 .. m) or writes outside out[0 .. m), every out[j] is written exactly once and every kernel terminates.  With
+ *     non-decreasing starts, some of which may exceed n, the result is as defined above; with starts that decrease somewhere the
+ *     values are unspecified;
+ *   - no value of one segment reaches another segment's output;
+ *   - no atomics, no read-back, no host wait: capturable into a step graph; scratch comes from ek_hip_malloc and is freed
+ *     stream-ordered;
+ *   - no kernel waits for another workgroup -- no ticket, no look-back, no polling loop;
+ *   - the route and every grid depend on (type, n, m, number of compute units, pointer alignment) only, never on the contents of
+ *     `starts`; the shape of every sum is a function of those and of `starts`: the result is bit-identical from run to run.
+ * ek_hip_reduce_segments_plan (host only, no device access; compute_units == 0: 256) reports the route, which is chosen from the
+ * mean length ceil(n / m): *route 0 nothing (m == 0), 1 grouped (n <= 1024 m: a workgroup owns a fixed number of consecutive
+ * segments, walks their entries in LDS tiles, *group_lanes = 2^ceil(log2(clamp(mean, 1, 64))) adjacent lanes per segment;
+ * *group_lanes == 0 otherwise), 2 one workgroup per segment, 3 split (fewer than 2 x compute_units segments of mean >= 16 Ki:
+ * *splits >= 2 pieces per segment, whose length follows the segment's own, and a packed fold of the partials; *splits == 1
+ * otherwise), and *workgroups, the grid of its first launch.
+ * ek_hip_repeat_segments is the transpose of the segment sum over n output entries:
+ *     out[i] = in[j] for the last j < m with starts[j] <= i (among equal starts: the non-empty segment), 0 if there is none
+ * -- gather(v, search_sorted(starts, arange(n), right) - 1) without the index array.  Keyed on the element size: I32 .. F64.
+ * m == 0: zeros; n == 0: nothing is launched.  Every out[i] is written exactly once, and no read leaves in[0 .. m) and
+ * starts[0 .. m), whatever `starts` holds; 16-byte stores wherever `out` allows.  The other guarantees hold as above.
+ * EK_OPTIONAL: enoki/hip.h asks for the entries' addresses first and throws without them. */
+EK_API EK_OPTIONAL int ek_hip_reduce_segments(int op, int type, void *out, const void *in, size_t n, const uint32_t *starts, size_t m);
+EK_API EK_OPTIONAL int ek_hip_repeat_segments(int type, void *out, const void *in, const uint32_t *starts, size_t m, size_t n);
+EK_API EK_OPTIONAL int ek_hip_reduce_segments_plan(int type, size_t n, size_t m, int compute_units, int *route, int *group_lanes, int *splits,
+                                                   size_t *workgroups);
 
 /* Stable sort of (key, element number) pairs by the low `key_bits` bits of 32-bit keys:
  *     keys_out = keys sorted ascending, perm_out[j] = original position of keys_out[j]; equal keys keep their order.
