@@ -53,6 +53,7 @@ EXPORTS = [
     "ek_hip_psum_blocks", "ek_hip_psum_blocks_plan",
     "ek_hip_sort_blocks", "ek_hip_sort_blocks_plan",
     "ek_hip_reduce_segments", "ek_hip_repeat_segments", "ek_hip_reduce_segments_plan",
+    "ek_hip_psum_segments", "ek_hip_psum_segments_plan",
 ]
 
 
@@ -654,6 +655,29 @@ def reduce_segments_plan(dtype, n, m, compute_units=0):
     check(lib.ek_hip_reduce_segments_plan(NP2EK[np.dtype(dtype)], ctypes.c_size_t(n), ctypes.c_size_t(m), int(compute_units),
                                           ctypes.byref(r), ctypes.byref(g), ctypes.byref(s), ctypes.byref(w)))
     return r.value, g.value, s.value, w.value
+
+
+def psum_segments(a, starts, exclusive=False, reverse=False, out=None):
+    """prefix sums inside the ragged segments that the uint32 array `starts` gives (ek_hip_psum_segments; starts[m] := a.n): entry i
+    of segment j becomes the sum of the segment's entries up to i, up to i - 1 with `exclusive`, from i on with `reverse`; entries in
+    front of starts[0] become 0.  `out`: write into this array (may be `a`)"""
+    if out is None:
+        out = Buf(a.dtype, a.n)
+    flags = (SCAN_EXCLUSIVE if exclusive else 0) | (SCAN_REVERSE if reverse else 0)
+    check(lib.ek_hip_psum_segments(a.ek, ctypes.c_void_p(out.ptr if a.n else None), ctypes.c_void_p(a.ptr if a.n else None),
+                                   ctypes.c_size_t(a.n), ctypes.c_void_p(starts.ptr if starts.n else None), ctypes.c_size_t(starts.n),
+                                   flags))
+    return out
+
+
+def psum_segments_plan(dtype, n, m, compute_units=0):
+    """(tile, tiles_per_workgroup, workgroups, launches): what ek_hip_psum_segments does for m segments of n entries of `dtype`
+    (host only; nothing but these numbers enters).  tile: output entries per LDS tile; a workgroup owns tiles_per_workgroup
+    consecutive tiles; launches: 1 for one workgroup, 3 otherwise; the last three are 0 for n == 0 or m == 0"""
+    t, p, w, l = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_int()
+    check(lib.ek_hip_psum_segments_plan(NP2EK[np.dtype(dtype)], ctypes.c_size_t(n), ctypes.c_size_t(m), int(compute_units),
+                                        ctypes.byref(t), ctypes.byref(p), ctypes.byref(w), ctypes.byref(l)))
+    return t.value, p.value, w.value, l.value
 
 
 class Bucketed:

@@ -292,6 +292,14 @@ template <typename Array> py::class_<Array> bind_array(py::module_ &m, const cha
               "values"_a, "starts"_a, "size"_a,
               "The transpose of segment_sum over `size` entries: result[i] = values[j] for the last j with starts[j] <= i, 0 in front "
               "of starts[0]; len(values) == len(starts).  Differentiable; the adjoint is segment_sum.");
+        m.def("segment_psum", [](const Array &a, const Starts &starts, bool exclusive, bool reverse) { return segment_psum(a, starts, exclusive, reverse); },
+              "array"_a, "starts"_a, "exclusive"_a = false, "reverse"_a = false,
+              "Prefix sums inside every ragged segment of a flat array (starts as for segment_sum): entry i of a segment becomes the sum "
+              "of the segment's entries up to i; with exclusive=True up to i - 1 (the segment's first entry is 0), with reverse=True "
+              "from i to the segment's end.  Entries in front of starts[0] become 0.  The transmittance in front of every sample that "
+              "compress() left of a ray is exp(-segment_psum(sigma * dt, starts, exclusive=True)).  One call, nothing subtracted, "
+              "bit-identical from run to run; float prefix sums are sums in a fixed tree order and need not ascend entry by entry.  "
+              "Differentiable; the adjoint is the same scan from the other end.");
     }
 
     if constexpr (IsFloat) {

@@ -679,6 +679,40 @@ template <typename Value> auto Tape<Value>::append_segment_repeat(Index source, 
     return target;
 }
 
+// segment_psum: BlockPrefixSum over ragged segments.  Entry i reaches exactly the outputs of its own segment on its other side, so
+// the adjoint is the same scan with the direction flipped and `exclusive` kept; forward applies the node's own scan to the source's
+// gradient.  The node keeps `starts`, as SegmentTranspose does, and releases it with the edge; `starts` carries no gradient.  An entry
+// in front of every segment reaches no output and gets +0, which is what the scan writes there.  A size-1 gradient is a broadcast
+// seed and is widened first.
+namespace detail {
+    template <typename TapeT, typename Value> struct SegmentPrefixSum : TapeT::Special {
+        typename TapeT::Offset starts;
+        bool exclusive, reverse;
+        SegmentPrefixSum(const typename TapeT::Offset &starts, bool exclusive, bool reverse)
+            : starts(starts), exclusive(exclusive), reverse(reverse) { }
+        Value apply(Value g, size_t size, bool rev) const {
+            if (g.size() == 1 && size != 1) set_slices(g, size);
+            return segment_psum(g, starts, exclusive, rev);
+        }
+        void forward(typename TapeT::Detail *detail, typename TapeT::Index target, const typename TapeT::Edge &edge) const override {
+            auto &s = detail->node(edge.source);
+            TapeT::Detail::accumulate(detail->node(target).grad, apply(s.grad, s.size, reverse));
+        }
+        void backward(typename TapeT::Detail *detail, typename TapeT::Index target, const typename TapeT::Edge &edge) const override {
+            auto &t = detail->node(target);
+            TapeT::Detail::accumulate(detail->node(edge.source).grad, apply(t.grad, t.size, !reverse));
+        }
+    };
+}
+
+template <typename Value> auto Tape<Value>::append_segment_psum(Index source, const Offset &starts, bool exclusive, bool reverse) -> Index {
+    if (source == 0) return 0;
+    Index target = append_node(d->node(source).size, "segment_psum");
+    d->node(target).edges.emplace_back(source, new detail::SegmentPrefixSum<Tape, Value>(starts, exclusive, reverse));
+    inc_ref_int(source, target);
+    return target;
+}
+
 // ---------------------------------------------------------------------------------------------
 //  Reference counting (autodiff.cpp:681-774)
 // ---------------------------------------------------------------------------------------------

@@ -1762,6 +1762,27 @@ template <typename T, typename Starts> inline T segment_repeat(const T &v, const
     } else throw std::runtime_error("segment_repeat(): not available for this array type");
 }
 
+/// Prefix sums inside every ragged segment (starts as for segment_sum): for entry i of segment j, segment_psum(x, starts)[i] =
+/// x[lo_j] + .. + x[i]; with `exclusive` the sum stops before entry i (the segment's first entry is +0), with `reverse` it runs
+/// from entry i to the segment's end.  Entries in front of starts[0] give +0.  The optical depth in front of every sample that
+/// compress() left of a ray is segment_psum(sigma * dt, starts, true).  One call, nothing subtracted, bit-identical from run to
+/// run; floating point prefix sums are sums in a fixed tree order and are NOT guaranteed to ascend entry by entry.  Differentiable
+/// in both modes (the adjoint is the same scan from the other end; `starts` carries no gradient).  An array type without the
+/// member throws at run time.
+namespace detail {
+    template <typename T, typename Starts, typename = void> struct has_segment_psum : std::false_type { };
+    template <typename T, typename Starts>
+    struct has_segment_psum<T, Starts, std::void_t<decltype(std::declval<const T &>().segment_psum_(std::declval<const Starts &>(), false, false))>>
+        : std::true_type { };
+}
+template <typename T, typename Starts> inline T segment_psum(const T &x, const Starts &starts, bool exclusive = false, bool reverse = false) {
+    static_assert(array_depth_v<T> == 1, "segment_psum(): takes a flat array");
+    if constexpr (detail::has_segment_psum<T, Starts>::value) {
+        static_assert(std::is_same_v<Starts, uint32_array_t<T>>, "segment_psum(): the starts are a UInt32 array");
+        return x.segment_psum_(starts, exclusive, reverse);
+    } else throw std::runtime_error("segment_psum(): not available for this array type");
+}
+
 /// Angle between two unit vectors / between a unit vector and the z axis, well behaved near 0 and pi (array_math.h:1404-1436)
 template <typename T> inline auto unit_angle(const T &a, const T &b) {
     auto dot_uv = dot(a, b);

@@ -137,6 +137,9 @@ template <typename Type> struct Tape {
     Index append_segment_sum(Index source, const Offset &starts);
     /// segment_repeat(source, starts, size): every entry once per entry of its segment; its adjoint is segment_sum()
     Index append_segment_repeat(Index source, const Offset &starts, size_t size);
+    /// segment_psum(source, starts, exclusive, reverse): prefix sums inside every ragged segment; its adjoint is the same scan from
+    /// the other end over the same starts, which the node keeps
+    Index append_segment_psum(Index source, const Offset &starts, bool exclusive, bool reverse);
     void set_scatter_gather_operand(Index *index, size_t size, bool permute);
 
     // ---- reference counting (ext = held by DiffArray handles, int = held by graph edges) ----
@@ -853,6 +856,16 @@ template <typename Type_> struct DiffArray : ArrayTag {
         Index idx = 0;
         if constexpr (Enabled) {
             if (m_index) idx = tape()->append_segment_repeat(m_index, starts.value_(), size);
+        }
+        return create(idx, std::move(result));
+    }
+
+    /// Prefix sums inside every ragged segment: one tape node of the source's size that keeps `starts` (Tape::append_segment_psum)
+    DiffArray segment_psum_(const ReplaceScalar<uint32_t> &starts, bool exclusive, bool reverse) const {
+        Type result = segment_psum(m_value, starts.value_(), exclusive, reverse);
+        Index idx = 0;
+        if constexpr (Enabled) {
+            if (m_index) idx = tape()->append_segment_psum(m_index, starts.value_(), exclusive, reverse);
         }
         return create(idx, std::move(result));
     }

@@ -1859,6 +1859,26 @@ template <typename Value_> struct HIPArray : ArrayTag {
         return r;
     }
 
+    /// Prefix sums inside every ragged segment (ek_hip_psum_segments; starts as for segment_reduce_, starts[m] := size()): entry i
+    /// of a segment becomes the sum of the segment's entries up to i, up to i - 1 with `exclusive` (the empty sum is +0), from i
+    /// on with `reverse`; entries in front of starts[0] become +0.  Unevaluated operands are evaluated once.
+    HIPArray segment_psum_(const HIPArray<uint32_t> &starts, bool exclusive, bool reverse) const {
+        static_assert(!IsMask, "segment_psum_(): not defined for masks");
+        if (!&ek_hip_psum_segments)
+            throw std::runtime_error("HIPArray::segment_psum_(): this C ABI has no entry ek_hip_psum_segments");
+        const size_t n = size(), m = starts.size();
+        if (n > 0xFFFFFFFFull || m > 0xFFFFFFFFull)
+            throw std::runtime_error("HIPArray::segment_psum_(): " + std::to_string(n) + " entries in " + std::to_string(m) +
+                                     " segments: more than 2^32 - 1 are not supported");
+        if (n == 0) return HIPArray();
+        if (m) starts.materialize();
+        materialize();
+        HIPArray r = empty_(n);
+        detail::hip_check(ek_hip_psum_segments(Type, r.m_buf->ptr, ptr_(), n, m ? (const uint32_t *) starts.ptr_() : nullptr, m,
+                                               (exclusive ? EK_SCAN_EXCLUSIVE : 0) | (reverse ? EK_SCAN_REVERSE : 0)), "segment_psum_");
+        return r;
+    }
+
     /// Prefix sums inside every block of `block` consecutive entries (ek_hip_psum_blocks): entry k of a block becomes the sum of
     /// its entries 0 .. k, 0 .. k - 1 with `exclusive` (the empty sum is +0), k .. block - 1 with `reverse`.  An unevaluated
     /// operand is evaluated once; a host scalar is an array of one entry.

@@ -690,6 +690,45 @@ EK_API EK_OPTIONAL int ek_hip_reduce_segments(int op, int type, void *out, const
 EK_API EK_OPTIONAL int ek_hip_repeat_segments(int type, void *out, const void *in, const uint32_t *starts, size_t m, size_t n);
 EK_API EK_OPTIONAL int ek_hip_reduce_segments_plan(int type, size_t n, size_t m, int compute_units, int *route, int *group_lanes, int *splits,
                                                    size_t *workgroups);
+/* Prefix sums inside ragged segments: the counterpart of ek_hip_psum_blocks for the segments of ek_hip_reduce_segments.  With
+ * starts[m] := n, segment j is [lo_j, hi_j) with lo_j = min(starts[j], n) and hi_j = max(lo_j, min(starts[j + 1], n)); for entry i
+ * of segment j
+ *     out[i] = in[lo_j] + .. + in[i]                    flags == 0
+ *              in[lo_j] + .. + in[i - 1]                EK_SCAN_EXCLUSIVE (the segment's first entry: +0)
+ *              in[i] + .. + in[hi_j - 1]                EK_SCAN_REVERSE
+ *              in[i + 1] + .. + in[hi_j - 1]            EK_SCAN_EXCLUSIVE | EK_SCAN_REVERSE (the segment's last entry: +0)
+ * -- the optical depth in front of every sample that compress() left of a ray, a CDF per segment -- where the whole-array
+ * spelling psum(x) - repeat_segments(gather(psum(x), starts), starts, n) takes four passes and subtracts two large running sums
+ * to get a small one.  The entries in front of min(starts[0], n) belong to no segment: their result is +0 in all four modes; with
+ * m == 0 the whole result is +0; n == 0: nothing is launched.  Empty segments own no entry and change nothing.  I32 .. F64
+ * (EK_BOOL or an unknown type: EK_ERR_UNSUPPORTED); integer sums wrap.  n or m above 2^32 - 1: EK_ERR_UNSUPPORTED; a flag bit
+ * other than the two, a null or misaligned `out` or `in` with n > 0, a null or misaligned `starts` with n > 0 and m > 0:
+ * EK_ERR_INVALID, before anything is launched.  out == in is allowed; any other overlap is the caller's error.
+ *   - every output is a sum of its own segment's terms only; nothing is ever subtracted;
+ *   - an inclusive entry with one term is its input bit for bit, -0.0 included;
+ *   - an exclusive entry IS the neighbouring inclusive entry of a call without EK_SCAN_EXCLUSIVE, moved and never recomputed:
+ *     entry i - 1 forward, entry i + 1 with EK_SCAN_REVERSE;
+ *   - a NaN or an infinity stays inside its segment; one in front of starts[0] reaches nothing;
+ *   - floating point prefix sums are sums in a fixed tree order: they are NOT guaranteed to ascend entry by entry;
+ *   - the shape of every sum is a function of (type, flags, n, m, pointer alignment, number of compute units) and of the contents
+ *     of `starts`: the result is bit-identical from run to run;
+ *   - no global atomics, no ticket, descriptor, look-back or polling loop, no kernel waits for another workgroup, no read-back and
+ *     no host wait; scratch comes from ek_hip_malloc and is freed stream-ordered: capturable into a step graph and replayable
+ *     with other contents in `starts`;
+ *   - `starts` is never validated (that would need a read-back): whatever it holds, every read lies inside in[0 .. n) and
+ *     starts[0 .. m), every entry of out[0 .. n) is written exactly once and nothing outside it, and every loop's trip count is
+ *     bounded by n, m or a constant.  Starts above n are clamped and give the result above; where `starts` decreases only the
+ *     values are unspecified.
+ * ONE output-driven route: a workgroup owns a run of consecutive tiles of *tile = 16 KiB / element size output entries, marks the
+ * starts that fall into a tile as head flags in LDS and scans (value, flag) pairs there; what reaches a workgroup's first tile from
+ * before it comes from two earlier launches (a total per workgroup, their scan by one workgroup).  ek_hip_psum_segments_plan
+ * (host only, no device access; compute_units == 0: 256) reports *tile, *tiles_per_workgroup = ceil(tiles / min(tiles,
+ * 4 x compute_units)) with tiles = ceil(n / *tile), *workgroups = ceil(tiles / *tiles_per_workgroup) and *launches (1 for one
+ * workgroup, 3 otherwise); the last three are 0 for n == 0 or m == 0.  Nothing but its arguments enters.
+ * EK_OPTIONAL: enoki/hip.h asks for the entries' addresses first and throws without them. */
+EK_API EK_OPTIONAL int ek_hip_psum_segments(int type, void *out, const void *in, size_t n, const uint32_t *starts, size_t m, int flags);
+EK_API EK_OPTIONAL int ek_hip_psum_segments_plan(int type, size_t n, size_t m, int compute_units, size_t *tile, size_t *tiles_per_workgroup,
+                                                 size_t *workgroups, int *launches);
 
 /* Stable sort of (key, element number) pairs by the low `key_bits` bits of 32-bit keys:
  *     keys_out = keys sorted ascending, perm_out[j] = original position of keys_out[j]; equal keys keep their order.
