@@ -54,6 +54,7 @@ EXPORTS = [
     "ek_hip_sort_blocks", "ek_hip_sort_blocks_plan",
     "ek_hip_reduce_segments", "ek_hip_repeat_segments", "ek_hip_reduce_segments_plan",
     "ek_hip_psum_segments", "ek_hip_psum_segments_plan",
+    "ek_hip_search_sorted_segments", "ek_hip_search_sorted_segments_plan",
 ]
 
 
@@ -678,6 +679,39 @@ def psum_segments_plan(dtype, n, m, compute_units=0):
     check(lib.ek_hip_psum_segments_plan(NP2EK[np.dtype(dtype)], ctypes.c_size_t(n), ctypes.c_size_t(m), int(compute_units),
                                         ctypes.byref(t), ctypes.byref(p), ctypes.byref(w), ctypes.byref(l)))
     return t.value, p.value, w.value, l.value
+
+
+def search_sorted_segments(table, table_starts, needles, needle_starts=None, rows=None, right=False, flat=False, out=None):
+    """per needle the number of entries of ITS ragged segment of `table` before it (right: not after it), uint32
+    (ek_hip_search_sorted_segments; segment j is table_starts[j] .. table_starts[j + 1], clamped, table_starts[m] := table.n).
+    needle_starts: needle e belongs to the last j with needle_starts[j] <= e (none in front of needle_starts[0]); rows: to segment
+    min(rows[e], m - 1); exactly one of the two.  flat: the position in `table` (the clamped start + the count)"""
+    if (needle_starts is None) == (rows is None):
+        raise ValueError("search_sorted_segments(): exactly one of needle_starts and rows names the needles' segments")
+    if out is None:
+        out = Buf(np.uint32, needles.n)
+    ptr = lambda b: ctypes.c_void_p(b.ptr if b.n else None)
+    owner = lambda b: ctypes.c_void_p(b.ptr) if b is not None else None     # (which of the two is given names the mode, also when empty)
+    check(lib.ek_hip_search_sorted_segments(table.ek, ptr(out) if needles.n else None, ptr(table), ctypes.c_size_t(table.n),
+                                            ptr(table_starts), ctypes.c_size_t(table_starts.n), ptr(needles), ctypes.c_size_t(needles.n),
+                                            owner(needle_starts), owner(rows), (SEARCH_RIGHT if right else 0) | (SEARCH_FLAT if flat else 0)))
+    return out
+
+
+SEARCH_RIGHT, SEARCH_FLAT = 1, 2
+SEGMENT_SEARCH_ROUTES = {0: "none", 1: "paired-tiles", 2: "indexed-lds", 3: "indexed-global"}
+
+
+def search_sorted_segments_plan(dtype, nt, m, n, indexed=False, compute_units=0):
+    """(route, tile_needles, tiles_per_workgroup, workgroups, lds_entries, window): what ek_hip_search_sorted_segments does for a
+    table of nt entries of `dtype` in m segments and n needles (host only; nothing but these numbers enters).  route: a key of
+    SEGMENT_SEARCH_ROUTES; lds_entries: the table entries one tile can stage (route 1) or the largest table that is staged whole
+    (routes 2 and 3); window: the starts one tile can stage (0 with rows)"""
+    r = ctypes.c_int()
+    v = [ctypes.c_size_t() for _ in range(5)]
+    check(lib.ek_hip_search_sorted_segments_plan(NP2EK[np.dtype(dtype)], ctypes.c_size_t(nt), ctypes.c_size_t(m), ctypes.c_size_t(n),
+                                                 int(bool(indexed)), int(compute_units), ctypes.byref(r), *[ctypes.byref(x) for x in v]))
+    return (r.value,) + tuple(x.value for x in v)
 
 
 class Bucketed:

@@ -86,50 +86,6 @@ static BlockSearchPlan block_search_plan(size_t elem_size, size_t R, size_t B, s
     return p;
 }
 
-/// `count` consecutive entries into LDS: 16-byte loads between an element-wise head and tail
-template <typename T> __device__ __forceinline__ void stage_entries(T *lds, const T *__restrict__ src, uint32_t count) {
-    constexpr uint32_t V = 16 / sizeof(T);
-    uint32_t head = head_of(src);
-    if (head > count) head = count;
-    if (threadIdx.x < head) lds[threadIdx.x] = src[threadIdx.x];
-    const uint32_t vecs = (count - head) / V;
-    for (uint32_t i = threadIdx.x; i < vecs; i += kSearchBlock) {
-        const Pack<T, V> pk = pack_load<T, V, false>(src + head + i * V);
-#pragma unroll
-        for (uint32_t k = 0; k < V; ++k) lds[head + i * V + k] = pk.v[k];
-    }
-    for (uint32_t i = head + vecs * V + threadIdx.x; i < count; i += kSearchBlock) lds[i] = src[i];
-}
-
-/// The workgroup searches needles [e0, e1): whole items of N between a peel to the first 16-byte aligned output and a tail.
-/// search(v, j, r): the results r of the needles v, the first of which is needle e0 + j.
-template <typename T, typename Search>
-__device__ __forceinline__ void search_range(uint32_t *__restrict__ out, const T *__restrict__ needles, size_t e0, size_t e1,
-                                             const Search &search) {
-    constexpr int N = kSearchLane;
-    const size_t count = e1 - e0;
-    size_t peel = head_of<size_t>(out + e0);
-    if (peel > count) peel = count;
-    const int vec = (reinterpret_cast<uintptr_t>(needles + e0 + peel) & 15u) == 0;
-    const size_t items = (count - peel) / N;
-    for (size_t item = threadIdx.x; item < items; item += kSearchBlock) {
-        const size_t j = peel + item * N;
-        T v[N];
-        search_load<T, N>(needles + e0 + j, vec, v);
-        Pack<uint32_t, N> r;
-        search(v, j, r.v);
-        pack_store<uint32_t, N, true>(out + e0 + j, r);
-    }
-    const uint32_t rest = (uint32_t) (count - items * N);          // peel + tail, at most 6
-    if (threadIdx.x < rest) {
-        const size_t j = threadIdx.x < peel ? threadIdx.x : items * N + threadIdx.x;
-        const T v[1] = { needles[e0 + j] };
-        uint32_t r[1];
-        search(v, j, r);
-        out[e0 + j] = r[0];
-    }
-}
-
 /// piece `piece` of `pieces` of `count` needles
 __device__ __forceinline__ size_t piece_begin(size_t count, uint32_t piece, uint32_t pieces) {
     return count / pieces * piece + min((size_t) piece, count % pieces);

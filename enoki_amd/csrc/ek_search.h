@@ -1,5 +1,6 @@
-// The search that search.hip (one sorted table) and block_search.hip (one sorted row per needle) share: the plan of the two-level
-// search, the predicate, the needle loads and N independent searches in lockstep.
+// The search that search.hip (one sorted table), block_search.hip (one sorted row per needle) and segment_search.hip (one ragged
+// segment per needle) share: the plan of the two-level search, the predicate, the needle loads, N independent searches in lockstep,
+// the staging of consecutive entries and the walk of a range of needles between its peel and its tail.
 //
 // A search is the branch-free fixed-trip form  pos += pred(T[pos + h - 1]) ? h : 0  for h = top, top / 2, .., 1 with the bound
 // test in the predicate; the trip count depends on the size of the searched range only, so no lane diverges.  Every read is
@@ -93,6 +94,50 @@ __device__ __forceinline__ void search_run(const T *lds, const uint32_t (&lds_ba
     }
 #pragma unroll
     for (int k = 0; k < N; ++k) result[k] = pos[k];
+}
+
+/// `count` consecutive entries into LDS: 16-byte loads between an element-wise head and tail
+template <typename T> __device__ __forceinline__ void stage_entries(T *lds, const T *__restrict__ src, uint32_t count) {
+    constexpr uint32_t V = 16 / sizeof(T);
+    uint32_t head = head_of(src);
+    if (head > count) head = count;
+    if (threadIdx.x < head) lds[threadIdx.x] = src[threadIdx.x];
+    const uint32_t vecs = (count - head) / V;
+    for (uint32_t i = threadIdx.x; i < vecs; i += kSearchBlock) {
+        const Pack<T, V> pk = pack_load<T, V, false>(src + head + i * V);
+#pragma unroll
+        for (uint32_t k = 0; k < V; ++k) lds[head + i * V + k] = pk.v[k];
+    }
+    for (uint32_t i = head + vecs * V + threadIdx.x; i < count; i += kSearchBlock) lds[i] = src[i];
+}
+
+/// The workgroup searches needles [e0, e1): whole items of N between a peel to the first 16-byte aligned output and a tail.
+/// search(v, j, r): the results r of the needles v, the first of which is needle e0 + j.
+template <typename T, typename Search>
+__device__ __forceinline__ void search_range(uint32_t *__restrict__ out, const T *__restrict__ needles, size_t e0, size_t e1,
+                                             const Search &search) {
+    constexpr int N = kSearchLane;
+    const size_t count = e1 - e0;
+    size_t peel = head_of<size_t>(out + e0);
+    if (peel > count) peel = count;
+    const int vec = (reinterpret_cast<uintptr_t>(needles + e0 + peel) & 15u) == 0;
+    const size_t items = (count - peel) / N;
+    for (size_t item = threadIdx.x; item < items; item += kSearchBlock) {
+        const size_t j = peel + item * N;
+        T v[N];
+        search_load<T, N>(needles + e0 + j, vec, v);
+        Pack<uint32_t, N> r;
+        search(v, j, r.v);
+        pack_store<uint32_t, N, true>(out + e0 + j, r);
+    }
+    const uint32_t rest = (uint32_t) (count - items * N);          // peel + tail, at most 6
+    if (threadIdx.x < rest) {
+        const size_t j = threadIdx.x < peel ? threadIdx.x : items * N + threadIdx.x;
+        const T v[1] = { needles[e0 + j] };
+        uint32_t r[1];
+        search(v, j, r);
+        out[e0 + j] = r[0];
+    }
 }
 
 /// the largest power of two <= count (0 for 0): the first step of a search over `count` entries

@@ -300,6 +300,21 @@ template <typename Array> py::class_<Array> bind_array(py::module_ &m, const cha
               "compress() left of a ray is exp(-segment_psum(sigma * dt, starts, exclusive=True)).  One call, nothing subtracted, "
               "bit-identical from run to run; float prefix sums are sums in a fixed tree order and need not ascend entry by entry.  "
               "Differentiable; the adjoint is the same scan from the other end.");
+        m.def("segment_search_sorted", [](const Array &table, const Starts &table_starts, const Array &needles,
+                                          const std::optional<Starts> &needle_starts, const std::optional<Starts> &rows, bool right, bool flat) {
+                  if (needle_starts.has_value() == rows.has_value())
+                      throw py::value_error("segment_search_sorted(): exactly one of needle_starts and rows names the needles' segments");
+                  return needle_starts ? segment_search_sorted(table, table_starts, needles, *needle_starts, right, flat)
+                                       : segment_search_sorted_indexed(table, table_starts, needles, *rows, right, flat);
+              }, "table"_a, "table_starts"_a, "needles"_a, "needle_starts"_a = py::none(), "rows"_a = py::none(), "right"_a = false,
+              "flat"_a = false,
+              "Every needle searched in its own ragged segment of a flat table (table_starts as for segment_sum; every segment sorted "
+              "ascending, e.g. a per-segment CDF from segment_psum): the UInt32 count of entries of the needle's segment before it "
+              "(right=True: not after it), 0 .. the segment's length; with flat=True the position in `table` (the segment's start + "
+              "the count), ready for gather.  needle_starts (UInt32, len(table_starts) entries): needle e belongs to the last j with "
+              "needle_starts[j] <= e, needles in front of needle_starts[0] give 0.  rows (UInt32, one per needle): needle e belongs "
+              "to segment min(rows[e], m - 1).  Exactly one of the two.  An empty segment and a NaN needle give 0.  One kernel, "
+              "nothing read back, bit-identical from run to run.  No gradient.");
     }
 
     if constexpr (IsFloat) {

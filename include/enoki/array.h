@@ -1783,6 +1783,39 @@ template <typename T, typename Starts> inline T segment_psum(const T &x, const S
     } else throw std::runtime_error("segment_psum(): not available for this array type");
 }
 
+/// Every needle searched in ITS OWN ragged segment of a flat table (table_starts as for segment_sum; every segment sorted
+/// ascending, e.g. the per-segment CDF that segment_psum wrote): the segment-local count of entries before the needle (`right`: not
+/// after it), 0 .. the segment's length, or with `flat` that count plus the segment's start -- the position in `table`, ready for
+/// gather.  segment_search_sorted: needle e belongs to the last j with needle_starts[j] <= e (segment_repeat's rule; size(needle_starts)
+/// == size(table_starts); needles in front of needle_starts[0] give 0).  segment_search_sorted_indexed: needle e belongs to segment
+/// min(rows[e], m - 1).  An empty segment and a NaN needle give 0.  One kernel, no row array, nothing read back; no gradient and no
+/// tape node.  An array type without the member throws at run time.
+namespace detail {
+    template <typename T, typename Starts, typename = void> struct has_segment_search_sorted : std::false_type { };
+    template <typename T, typename Starts>
+    struct has_segment_search_sorted<T, Starts, std::void_t<decltype(std::declval<const T &>().segment_search_sorted_(
+        std::declval<const Starts &>(), std::declval<const T &>(), (const Starts *) nullptr, (const Starts *) nullptr, false, false))>>
+        : std::true_type { };
+}
+template <typename Table, typename Starts>
+inline auto segment_search_sorted(const Table &table, const Starts &table_starts, const Table &needles, const Starts &needle_starts,
+                                   bool right = false, bool flat = false) {
+    static_assert(array_depth_v<Table> == 1, "segment_search_sorted(): the table is a flat array");
+    if constexpr (detail::has_segment_search_sorted<Table, Starts>::value) {
+        static_assert(std::is_same_v<Starts, uint32_array_t<Table>>, "segment_search_sorted(): the starts are UInt32 arrays");
+        return uint32_array_t<Table>(table.segment_search_sorted_(table_starts, needles, &needle_starts, (const Starts *) nullptr, right, flat));
+    } else throw std::runtime_error("segment_search_sorted(): not available for this array type");
+}
+template <typename Table, typename Starts>
+inline auto segment_search_sorted_indexed(const Table &table, const Starts &table_starts, const Table &needles, const Starts &rows,
+                                           bool right = false, bool flat = false) {
+    static_assert(array_depth_v<Table> == 1, "segment_search_sorted_indexed(): the table is a flat array");
+    if constexpr (detail::has_segment_search_sorted<Table, Starts>::value) {
+        static_assert(std::is_same_v<Starts, uint32_array_t<Table>>, "segment_search_sorted_indexed(): the starts and rows are UInt32 arrays");
+        return uint32_array_t<Table>(table.segment_search_sorted_(table_starts, needles, (const Starts *) nullptr, &rows, right, flat));
+    } else throw std::runtime_error("segment_search_sorted_indexed(): not available for this array type");
+}
+
 /// Angle between two unit vectors / between a unit vector and the z axis, well behaved near 0 and pi (array_math.h:1404-1436)
 template <typename T> inline auto unit_angle(const T &a, const T &b) {
     auto dot_uv = dot(a, b);

@@ -897,6 +897,15 @@ template <typename Type_> struct DiffArray : ArrayTag {
         return ReplaceScalar<uint32_t>(m_value.block_search_sorted_(needles.m_value, block, right, &rows->value_()));
     }
 
+    /// ... and in the needle's own ragged segment (the starts and `rows` are themselves without gradient): nothing is recorded
+    ReplaceScalar<uint32_t> segment_search_sorted_(const ReplaceScalar<uint32_t> &table_starts, const DiffArray &needles,
+                                                   const ReplaceScalar<uint32_t> *needle_starts, const ReplaceScalar<uint32_t> *rows,
+                                                   bool right, bool flat) const {
+        return ReplaceScalar<uint32_t>(m_value.segment_search_sorted_(table_starts.value_(), needles.m_value,
+                                                                      needle_starts ? &needle_starts->value_() : nullptr,
+                                                                      rows ? &rows->value_() : nullptr, right, flat));
+    }
+
     // -----------------------------------------------------------------------------------------
     //  Initializers (forwarded), storage access
     // -----------------------------------------------------------------------------------------

@@ -1879,6 +1879,48 @@ template <typename Value_> struct HIPArray : ArrayTag {
         return r;
     }
 
+    /// Per needle the number of entries of ITS ragged segment of this array before it (`right`: not after it), a segment-local
+    /// value, or with `flat` the position in this array, in one launch (ek_hip_search_sorted_segments; table_starts as for
+    /// segment_reduce_).  Exactly one of `needle_starts` (as many entries as table_starts: needle e belongs to the last j with
+    /// needle_starts[j] <= e) and `rows` (one segment per needle, clamped to the last) names the needles' segments.  Unevaluated
+    /// operands are evaluated once; no needles make no call.
+    HIPArray<uint32_t> segment_search_sorted_(const HIPArray<uint32_t> &table_starts, const HIPArray &needles,
+                                              const HIPArray<uint32_t> *needle_starts, const HIPArray<uint32_t> *rows, bool right,
+                                              bool flat) const {
+        static_assert(!IsMask, "segment_search_sorted_(): not defined for masks");
+        if (!&ek_hip_search_sorted_segments)
+            throw std::runtime_error("HIPArray::segment_search_sorted_(): this C ABI has no entry ek_hip_search_sorted_segments");
+        if ((needle_starts != nullptr) == (rows != nullptr))
+            throw std::runtime_error("HIPArray::segment_search_sorted_(): exactly one of needle_starts and rows names the needles' segments");
+        const size_t nt = size(), m = table_starts.size(), n = needles.size();
+        if (needle_starts && needle_starts->size() != m)
+            throw std::runtime_error("HIPArray::segment_search_sorted_(): " + std::to_string(needle_starts->size()) +
+                                     " needle starts do not match " + std::to_string(m) + " table starts");
+        if (rows && rows->size() != n)
+            throw std::runtime_error("HIPArray::segment_search_sorted_(): " + std::to_string(n) + " needles do not match " +
+                                     std::to_string(rows->size()) + " row indices");
+        if (nt > 0xFFFFFFFFull || m > 0xFFFFFFFFull || n > 0xFFFFFFFFull)
+            throw std::runtime_error("HIPArray::segment_search_sorted_(): " + std::to_string(nt) + " entries, " + std::to_string(m) +
+                                     " segments, " + std::to_string(n) + " needles: more than 2^32 - 1 are not supported");
+        if (rows && m == 0 && n != 0) throw std::runtime_error("HIPArray::segment_search_sorted_(): needles and no segment to search");
+        if (n == 0) return HIPArray<uint32_t>();
+        needles.materialize();
+        if (m) {
+            table_starts.materialize();
+            if (needle_starts) needle_starts->materialize();
+        }
+        if (rows) rows->materialize();
+        if (nt) materialize();
+        HIPArray<uint32_t> result = HIPArray<uint32_t>::empty_(n);
+        detail::hip_check(ek_hip_search_sorted_segments(Type, (uint32_t *) result.m_buf->ptr, nt ? ptr_() : nullptr, nt,
+                                                        m ? (const uint32_t *) table_starts.ptr_() : nullptr, m, needles.ptr_(), n,
+                                                        needle_starts && m ? (const uint32_t *) needle_starts->ptr_() : nullptr,
+                                                        rows ? (const uint32_t *) rows->ptr_() : nullptr,
+                                                        (right ? EK_SEARCH_RIGHT : 0) | (flat ? EK_SEARCH_FLAT : 0)),
+                          "segment_search_sorted_");
+        return result;
+    }
+
     /// Prefix sums inside every block of `block` consecutive entries (ek_hip_psum_blocks): entry k of a block becomes the sum of
     /// its entries 0 .. k, 0 .. k - 1 with `exclusive` (the empty sum is +0), k .. block - 1 with `reverse`.  An unevaluated
     /// operand is evaluated once; a host scalar is an array of one entry.

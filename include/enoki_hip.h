@@ -729,6 +729,47 @@ EK_API EK_OPTIONAL int ek_hip_reduce_segments_plan(int type, size_t n, size_t m,
 EK_API EK_OPTIONAL int ek_hip_psum_segments(int type, void *out, const void *in, size_t n, const uint32_t *starts, size_t m, int flags);
 EK_API EK_OPTIONAL int ek_hip_psum_segments_plan(int type, size_t n, size_t m, int compute_units, size_t *tile, size_t *tiles_per_workgroup,
                                                  size_t *workgroups, int *launches);
+/* Every needle searched in ITS OWN ragged segment of a flat table: the counterpart of ek_hip_search_sorted_blocks for the segments
+ * of ek_hip_reduce_segments, and the call that reads the per-segment CDF that ek_hip_psum_segments writes.  With
+ * table_starts[m] := nt, segment j is [lo_j, hi_j) with lo_j = min(table_starts[j], nt) and hi_j = max(lo_j,
+ * min(table_starts[j + 1], nt)); every segment is expected to be sorted ascending and free of NaN, the segments need not be ordered
+ * against each other.  The segment of needle e is named in exactly one of two ways:
+ *   needle_starts (m entries)   the last j with needle_starts[j] <= e, the rule of ek_hip_repeat_segments: segment j gets
+ *                               needle_starts[j + 1] - needle_starts[j] consecutive needles, none is allowed; a needle in front of
+ *                               needle_starts[0] has no segment.  m == 0: no needle has one, and needle_starts may be null;
+ *   row_index (n entries)       segment min(row_index[e], m - 1); m == 0 with n != 0: EK_ERR_INVALID.
+ *     out[e] = the number of entries t of the needle's segment with t < needles[e]      flags == 0
+ *              ... with t <= needles[e]                                                  EK_SEARCH_RIGHT
+ *              lo_j + that number, the position in `table` (it may equal hi_j)           EK_SEARCH_FLAT
+ * A needle without a segment, an empty segment and a NaN needle yield 0 (the comparisons are the type's own); nt == 0 yields
+ * zeros; n == 0: nothing is launched.  For every other needle, on sorted segments, out[e] is numpy.searchsorted(table[lo_j:hi_j],
+ * needles[e], side) bit for bit.  I32 .. F64, table and needles of the same type (EK_BOOL or an unknown type:
+ * EK_ERR_UNSUPPORTED); nt, m or n above 2^32 - 1: EK_ERR_UNSUPPORTED; a flag bit other than the two, both owners or (with m != 0)
+ * neither, a null `out`, `needles`, `table` (nt > 0) or `table_starts` (m > 0) with n > 0, a pointer that is no multiple of its
+ * element size: EK_ERR_INVALID, before anything is launched.
+ *   - no atomics, no scratch memory, no read-back, no host wait, no kernel waits for another workgroup: capturable into a step
+ *     graph and replayable with other contents in all three index arrays; bit-identical from run to run;
+ *   - the index arrays are never validated (that would need a read-back): whatever they hold, every read lies inside
+ *     table[0 .. nt), the starts' [0 .. m) and needles' and row_index' [0 .. n), every entry of out[0 .. n) is written exactly
+ *     once and nothing outside it, every loop's trip count is bounded by a constant, log2(nt) or log2(m), and every result lies in
+ *     0 .. hi_j - lo_j of the clamped segment the needle was assigned to (with EK_SEARCH_FLAT in 0 .. nt).  Where starts decrease or
+ *     a segment is not sorted only the VALUES are unspecified.
+ * Three routes, chosen from (type, nt, m, n, compute units) alone: 1 paired tiles (needle_starts: a workgroup owns consecutive
+ * tiles of *tile_needles needles, stages a window of at most *window starts of both arrays and at most *lds_entries table entries
+ * of the tile's segments in LDS; a needle whose clamped segment is not staged is searched in global memory), 2 indexed with the
+ * table staged whole (row_index, nt <= *lds_entries), 3 indexed in global memory.  ek_hip_search_sorted_segments_plan (host only,
+ * no device access; indexed != 0: with a row_index; compute_units == 0: 256) reports them with *tiles_per_workgroup =
+ * ceil(tiles / min(tiles, 2 x compute_units)), tiles = ceil(n / *tile_needles), and *workgroups = ceil(tiles /
+ * *tiles_per_workgroup); *window is 0 for routes 2 and 3; n == 0: route 0 and no workgroups.  Nothing but its arguments enters.
+ * EK_OPTIONAL: enoki/hip.h asks for the entries' addresses first and throws without them. */
+#define EK_SEARCH_RIGHT 1
+#define EK_SEARCH_FLAT  2
+EK_API EK_OPTIONAL int ek_hip_search_sorted_segments(int type, uint32_t *out, const void *table, size_t nt, const uint32_t *table_starts,
+                                                     size_t m, const void *needles, size_t n, const uint32_t *needle_starts,
+                                                     const uint32_t *row_index, int flags);
+EK_API EK_OPTIONAL int ek_hip_search_sorted_segments_plan(int type, size_t nt, size_t m, size_t n, int indexed, int compute_units, int *route,
+                                                          size_t *tile_needles, size_t *tiles_per_workgroup, size_t *workgroups,
+                                                          size_t *lds_entries, size_t *window);
 
 /* Stable sort of (key, element number) pairs by the low `key_bits` bits of 32-bit keys:
  *     keys_out = keys sorted ascending, perm_out[j] = original position of keys_out[j]; equal keys keep their order.
