@@ -55,6 +55,7 @@ EXPORTS = [
     "ek_hip_reduce_segments", "ek_hip_repeat_segments", "ek_hip_reduce_segments_plan",
     "ek_hip_psum_segments", "ek_hip_psum_segments_plan",
     "ek_hip_search_sorted_segments", "ek_hip_search_sorted_segments_plan",
+    "ek_hip_sort_segments", "ek_hip_sort_segments_plan",
 ]
 
 
@@ -712,6 +713,37 @@ def search_sorted_segments_plan(dtype, nt, m, n, indexed=False, compute_units=0)
     check(lib.ek_hip_search_sorted_segments_plan(NP2EK[np.dtype(dtype)], ctypes.c_size_t(nt), ctypes.c_size_t(m), ctypes.c_size_t(n),
                                                  int(bool(indexed)), int(compute_units), ctypes.byref(r), *[ctypes.byref(x) for x in v]))
     return (r.value,) + tuple(x.value for x in v)
+
+
+def sort_segments(a, starts, descending=False, flat=False, values=True, index=True, out_values=None, out_index=None, flags=None):
+    """stable sort inside the ragged segments that the uint32 array `starts` gives (ek_hip_sort_segments; starts[m] := a.n): returns
+    (values, index), None for an output that was not asked for.  index: uint32, the segment-local position of the entry at each
+    slot, its flat position with `flat`; entries in front of starts[0] stay where they are.  out_values / out_index: write into
+    these arrays (they must not overlap `a` or each other); flags: the raw flag word instead of descending / flat"""
+    if values and out_values is None:
+        out_values = Buf(a.dtype, a.n)
+    if index and out_index is None:
+        out_index = Buf(np.uint32, a.n)
+    if flags is None:
+        flags = (SORT_DESCENDING if descending else 0) | (SORT_FLAT_INDEX if flat else 0)
+    check(lib.ek_hip_sort_segments(a.ek, ctypes.c_void_p(out_values.ptr if out_values is not None else None),
+                                   ctypes.c_void_p(out_index.ptr if out_index is not None else None),
+                                   ctypes.c_void_p(a.ptr if a.n else None), ctypes.c_size_t(a.n),
+                                   ctypes.c_void_p(starts.ptr if starts.n else None), ctypes.c_size_t(starts.n), int(flags)))
+    return out_values, out_index
+
+
+def sort_segments_plan(dtype, n, m, want_index=True, compute_units=0):
+    """(tile, tiles, tiles_per_workgroup, workgroups, merges, merge_workgroups, launches, scratch_bytes): what ek_hip_sort_segments
+    does for m segments of n entries of `dtype` (host only; nothing but these numbers enters).  tile: entries per LDS tile; a
+    workgroup owns tiles_per_workgroup consecutive tiles; merges = ceil(log2(tiles)) merge launches of merge_workgroups workgroups;
+    launches: 1 for one tile, 2 + merges otherwise; all but tile are 0 for n == 0 or m == 0"""
+    t, ts, p, w, mw, s = (ctypes.c_size_t() for _ in range(6))
+    mg, l = ctypes.c_int(), ctypes.c_int()
+    check(lib.ek_hip_sort_segments_plan(NP2EK[np.dtype(dtype)], ctypes.c_size_t(n), ctypes.c_size_t(m), int(bool(want_index)),
+                                        int(compute_units), ctypes.byref(t), ctypes.byref(ts), ctypes.byref(p), ctypes.byref(w),
+                                        ctypes.byref(mg), ctypes.byref(mw), ctypes.byref(l), ctypes.byref(s)))
+    return t.value, ts.value, p.value, w.value, mg.value, mw.value, l.value, s.value
 
 
 class Bucketed:

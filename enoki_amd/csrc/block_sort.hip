@@ -50,7 +50,8 @@
 //                        Scratch: one or two buffers of n composites from ek_hip_malloc, freed stream-ordered.
 // Grids are capped; every kernel walks its tiles / segments in a grid-stride loop.  Positions are 32-bit (n < 2^32), global offsets
 // size_t.  An output that was not asked for is neither computed into memory nor allocated.
-#include "ek_block.h"
+// (The composites, the network and the two searches of a merge live in ek_sort.h, which segment_sort.hip shares.)
+#include "ek_sort.h"
 
 namespace ek {
 
@@ -60,8 +61,6 @@ constexpr uint32_t kSortChunk4 = 8192, kSortChunk8 = 4096;   // routes 2, 3: ent
 constexpr uint32_t kSortMergeTile = 2048;          // route 3: outputs per merge tile; divides both chunk sizes
 constexpr size_t kSortMaxGrid = 0x7FFFFFFFull;
 constexpr size_t kSortMaxEntries = 0xFFFFFFFFull;
-
-enum { kSortUnsigned = 0, kSortSigned = 1, kSortFloat = 2 };
 
 struct SortPlan {
     int route, merge_passes;
@@ -92,82 +91,6 @@ static SortPlan sort_plan(size_t elem, size_t n, size_t B) {
         p.workgroups = std::min(m * runs, kSortMaxGrid);
     }
     return p;
-}
-
-// ---- composites --------------------------------------------------------------------------------------------------------------
-template <int ES> struct SortComp;
-template <> struct SortComp<4> { uint64_t w; };
-template <> struct SortComp<8> { uint64_t key; uint32_t pos; };
-
-__device__ __forceinline__ bool comp_less(const SortComp<4> &a, const SortComp<4> &b) { return a.w < b.w; }
-__device__ __forceinline__ bool comp_less(const SortComp<8> &a, const SortComp<8> &b) {
-    return a.key < b.key || (a.key == b.key && a.pos < b.pos);
-}
-__device__ __forceinline__ uint32_t comp_pos(const SortComp<4> &c) { return (uint32_t) c.w; }
-__device__ __forceinline__ uint32_t comp_pos(const SortComp<8> &c) { return c.pos; }
-
-template <int ES> __device__ __forceinline__ SortComp<ES> comp_padding() {
-    if constexpr (ES == 4) return SortComp<4>{ ~0ull };
-    else return SortComp<8>{ ~0ull, ~0u };
-}
-
-template <int ES, int KIND, typename U> __device__ __forceinline__ SortComp<ES> comp_make(U u, uint32_t pos, bool desc) {
-    constexpr U kSign = U(1) << (ES * 8 - 1), kOnes = ~U(0);
-    U key;
-    if constexpr (KIND == kSortFloat) {
-        constexpr U kInf = ES == 4 ? U(0x7F800000u) : U(0x7FF0000000000000ull);
-        if ((u & ~kSign) > kInf) {
-            key = kOnes;
-        } else {
-            if (u == kSign) u = 0;
-            key = u ^ ((u & kSign) ? kOnes : kSign);
-            if (desc) key = ~key;
-        }
-    } else {
-        key = KIND == kSortSigned ? U(u ^ kSign) : u;
-        if (desc) key = ~key;
-    }
-    if constexpr (ES == 4) return SortComp<4>{ ((uint64_t) key << 32) | pos };
-    else return SortComp<8>{ key, pos };
-}
-
-/// `count` composites in LDS or in scratch: 4-byte types one array of words, 8-byte types the keys followed by the positions
-template <int ES> struct CompStore {
-    uint64_t *a;
-    uint32_t *b;
-    __device__ __forceinline__ SortComp<ES> get(size_t i) const {
-        if constexpr (ES == 4) return SortComp<4>{ a[i] };
-        else return SortComp<8>{ a[i], b[i] };
-    }
-    __device__ __forceinline__ void set(size_t i, const SortComp<ES> &c) const {
-        if constexpr (ES == 4) a[i] = c.w;
-        else { a[i] = c.key; b[i] = c.pos; }
-    }
-};
-template <int ES> __host__ __device__ __forceinline__ CompStore<ES> comp_store(void *base, size_t count) {
-    uint64_t *a = (uint64_t *) base;
-    return CompStore<ES>{ a, (uint32_t *) (a + count) };
-}
-constexpr size_t comp_bytes(int es) { return es == 4 ? 8 : 12; }
-
-/// Bitonic network over `slots` composites in LDS, a multiple of P = 2^k: every aligned run of P slots ends ascending.  A pair is
-/// (lo, lo | j) with j < P: it never crosses a run.  All lanes of the workgroup call this; the slots are written and a barrier
-/// has passed; it ends with a barrier.
-/// (The stages with j <= 64 exchange inside one wave's 128 slots and could do with a wavefront-scope fence instead of the barrier:
-/// tried, and it changed no time -- the stages are bound by their LDS traffic, not by the barriers.)
-template <int ES> __device__ __forceinline__ void sort_bitonic(const CompStore<ES> &s, uint32_t slots, uint32_t P) {
-    const uint32_t half = slots >> 1;
-    for (uint32_t k = 2; k <= P; k <<= 1) {
-        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-            for (uint32_t t = threadIdx.x; t < half; t += blockDim.x) {
-                const uint32_t lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
-                const bool up = ((lo & (P - 1)) & k) == 0;
-                const SortComp<ES> x = s.get(lo), y = s.get(hi);
-                if (comp_less(y, x) == up) { s.set(lo, y); s.set(hi, x); }
-            }
-            __syncthreads();
-        }
-    }
 }
 
 // ---- route 1: packed ---------------------------------------------------------------------------------------------------------
@@ -282,29 +205,6 @@ __global__ __launch_bounds__(1024) void k_sort_chunks(U *outv, uint32_t *outi, C
 }
 
 // ---- route 3, launches 2 ..: merge the adjacent runs of `run` entries of every row --------------------------------------------
-/// how many of the first d entries of the merge of A (la entries) and B (lb entries) come from A; d <= la + lb
-template <int ES>
-__device__ __forceinline__ uint32_t sort_merge_path(const CompStore<ES> &s, size_t a, uint32_t la, size_t b, uint32_t lb, uint32_t d) {
-    uint32_t lo = d > lb ? d - lb : 0, hi = d < la ? d : la;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);          // mid < la; 0 <= d - 1 - mid < lb
-        if (comp_less(s.get(a + mid), s.get(b + (d - 1 - mid)))) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-/// number of the `count` ascending composites from slot `first` on that are less than c
-template <int ES> __device__ __forceinline__ uint32_t sort_rank(const CompStore<ES> &s, uint32_t first, uint32_t count, const SortComp<ES> &c) {
-    uint32_t lo = 0, hi = count;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (comp_less(s.get(first + mid), c)) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 template <typename U>
 __global__ __launch_bounds__(256) void k_sort_merge(U *outv, uint32_t *outi, CompStore<sizeof(U)> dst, CompStore<sizeof(U)> src, const U *in,
                                                     size_t B, size_t run, size_t tiles_per_row, size_t tiles, int flags) {
@@ -408,11 +308,6 @@ static int sort_shape_check(const char *what, size_t n, size_t block) {
     if (int rc = blocks_shape_check(what, n, block)) return rc;
     if (n > kSortMaxEntries) return fail(EK_ERR_UNSUPPORTED, "%s: %zu entries, more than 2^32 - 1", what, n);
     return EK_OK;
-}
-
-static bool sort_overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return a && b && x < y + nb && y < x + na;
 }
 
 } // namespace ek

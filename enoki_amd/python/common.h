@@ -315,6 +315,20 @@ template <typename Array> py::class_<Array> bind_array(py::module_ &m, const cha
               "needle_starts[j] <= e, needles in front of needle_starts[0] give 0.  rows (UInt32, one per needle): needle e belongs "
               "to segment min(rows[e], m - 1).  Exactly one of the two.  An empty segment and a NaN needle give 0.  One kernel, "
               "nothing read back, bit-identical from run to run.  No gradient.");
+        // stable sort inside every ragged segment; segment_sort is differentiable, segment_argsort returns UInt32 and has no gradient
+        m.def("segment_sort", [](const Array &a, const Starts &starts, bool descending) { return segment_sort(a, starts, descending); },
+              "array"_a, "starts"_a, "descending"_a = false,
+              "Stable sort inside every ragged segment of a flat array (starts as for segment_sum): ascending by <, with descending by "
+              ">; equal entries keep their input order, -0.0 == +0.0, every NaN comes last.  Per segment the order of "
+              "numpy.argsort(segment, kind='stable').  Entries in front of starts[0] stay where they are.  "
+              "segment_sort(segment_psum(w, starts), starts) is a per-segment CDF that does ascend, as segment_search_sorted expects.  "
+              "One call, nothing read back, bit-identical from run to run.  Differentiable; starts carries no gradient.");
+        m.def("segment_argsort", [](const Array &a, const Starts &starts, bool descending, bool flat) {
+                  return segment_argsort(a, starts, descending, flat);
+              }, "array"_a, "starts"_a, "descending"_a = false, "flat"_a = false,
+              "The permutation of segment_sort as UInt32: per output slot the segment-local position of the entry that lands there; "
+              "with flat=True its position in the flat array, ready for gather(other, p).  An entry in front of starts[0] gives its own "
+              "position in both modes.  No gradient.");
     }
 
     if constexpr (IsFloat) {

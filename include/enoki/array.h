@@ -1816,6 +1816,41 @@ inline auto segment_search_sorted_indexed(const Table &table, const Starts &tabl
     } else throw std::runtime_error("segment_search_sorted_indexed(): not available for this array type");
 }
 
+/// Stable sort inside every ragged segment of a flat array (starts as for segment_sum): block_sort's order -- ascending by `<`,
+/// with `descending` by `>`; entries that compare equal keep their input order, -0.0 == +0.0 (each keeps its bits), every NaN comes
+/// after all numbers in both directions -- per segment numpy.argsort(segment, kind="stable").  Entries in front of starts[0] stay
+/// where they are.  segment_sort returns the values: a ray's hits in depth order once rays keep different counts, and
+/// segment_sort(segment_psum(w, starts), starts) a per-segment CDF that does ascend, as segment_search_sorted expects.
+/// segment_argsort returns the permutation as a UInt32 array: the segment-local position of the entry at each slot, or with `flat`
+/// its position in the flat array, so that gather(other, segment_argsort(t, starts, false, true)) reorders another array along (an
+/// entry in front of starts[0] gives its own position in both modes).  One call each, nothing read back, bit-identical from run to
+/// run; segment_sort is differentiable (its adjoint is a scatter through the permutation; `starts` carries no gradient),
+/// segment_argsort has no gradient.  An array type without the members throws at run time.
+namespace detail {
+    template <typename T, typename Starts, typename = void> struct has_segment_sort : std::false_type { };
+    template <typename T, typename Starts>
+    struct has_segment_sort<T, Starts, std::void_t<decltype(std::declval<const T &>().segment_sort_(std::declval<const Starts &>(), false))>>
+        : std::true_type { };
+    template <typename T, typename Starts, typename = void> struct has_segment_argsort : std::false_type { };
+    template <typename T, typename Starts>
+    struct has_segment_argsort<T, Starts, std::void_t<decltype(std::declval<const T &>().segment_argsort_(std::declval<const Starts &>(), false, false))>>
+        : std::true_type { };
+}
+template <typename T, typename Starts> inline T segment_sort(const T &x, const Starts &starts, bool descending = false) {
+    static_assert(array_depth_v<T> == 1, "segment_sort(): takes a flat array");
+    if constexpr (detail::has_segment_sort<T, Starts>::value) {
+        static_assert(std::is_same_v<Starts, uint32_array_t<T>>, "segment_sort(): the starts are a UInt32 array");
+        return x.segment_sort_(starts, descending);
+    } else throw std::runtime_error("segment_sort(): not available for this array type");
+}
+template <typename T, typename Starts> inline auto segment_argsort(const T &x, const Starts &starts, bool descending = false, bool flat = false) {
+    static_assert(array_depth_v<T> == 1, "segment_argsort(): takes a flat array");
+    if constexpr (detail::has_segment_argsort<T, Starts>::value) {
+        static_assert(std::is_same_v<Starts, uint32_array_t<T>>, "segment_argsort(): the starts are a UInt32 array");
+        return uint32_array_t<T>(x.segment_argsort_(starts, descending, flat));
+    } else throw std::runtime_error("segment_argsort(): not available for this array type");
+}
+
 /// Angle between two unit vectors / between a unit vector and the z axis, well behaved near 0 and pi (array_math.h:1404-1436)
 template <typename T> inline auto unit_angle(const T &a, const T &b) {
     auto dot_uv = dot(a, b);

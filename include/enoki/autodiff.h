@@ -870,6 +870,25 @@ template <typename Type_> struct DiffArray : ArrayTag {
         return create(idx, std::move(result));
     }
 
+    /// Stable sort inside every ragged segment: a tracked source asks the one sorting call for the flat permutation as well and
+    /// records block_sort's tape node, which keeps it (Tape::append_block_sort: forward gathers through the permutation, backward
+    /// scatters into zeros); an untracked source sorts values only.  `starts` carries no gradient.
+    DiffArray segment_sort_(const ReplaceScalar<uint32_t> &starts, bool descending) const {
+        if constexpr (Enabled && detail::has_segment_sort<Type, uint32_array_t<Type>>::value) {
+            if (m_index) {
+                uint32_array_t<Type> perm;
+                Type result = m_value.segment_sort_(starts.value_(), descending, &perm);
+                return create(tape()->append_block_sort(m_index, perm), std::move(result));
+            }
+        }
+        return create(0, segment_sort(m_value, starts.value_(), descending));
+    }
+
+    /// The permutation is piecewise constant in the entries: computed on the detached values, no node, no edges
+    ReplaceScalar<uint32_t> segment_argsort_(const ReplaceScalar<uint32_t> &starts, bool descending, bool flat) const {
+        return ReplaceScalar<uint32_t>(segment_argsort(m_value, starts.value_(), descending, flat));
+    }
+
     DiffArray segment_prod_(const ReplaceScalar<uint32_t> &starts) const {
         if (Enabled && m_index != 0) throw std::runtime_error("DiffArray::segment_prod_(): gradients not implemented");
         return create(0, segment_prod(m_value, starts.value_()));

@@ -1921,6 +1921,48 @@ template <typename Value_> struct HIPArray : ArrayTag {
         return result;
     }
 
+    /// Stable sort inside every ragged segment (ek_hip_sort_segments; starts as for segment_reduce_, starts[m] := size()): the
+    /// order of block_sort_ -- ascending by `<`, by `>` with `descending`; equal entries keep their input order, -0.0 == +0.0,
+    /// every NaN comes last; the entries' own bits.  Entries in front of starts[0] stay where they are.  With `flat_perm` the same
+    /// call also writes the permutation as positions in the flat array: result == gather(*this, *flat_perm).  Unevaluated operands
+    /// are evaluated once; no entries make no call.
+    HIPArray segment_sort_(const HIPArray<uint32_t> &starts, bool descending, HIPArray<uint32_t> *flat_perm = nullptr) const {
+        HIPArray values;
+        sort_segments_("segment_sort_", starts, (descending ? EK_SORT_DESCENDING : 0) | EK_SORT_FLAT_INDEX, &values, flat_perm);
+        return values;
+    }
+
+    /// ... and the permutation alone: per output slot the segment-local position of the entry that lands there, or with `flat`
+    /// its position in the flat array, ready for gather(other, p); an entry in front of starts[0] gives its own position in both
+    /// modes.  No values are written.
+    HIPArray<uint32_t> segment_argsort_(const HIPArray<uint32_t> &starts, bool descending, bool flat) const {
+        HIPArray<uint32_t> index;
+        sort_segments_("segment_argsort_", starts, (descending ? EK_SORT_DESCENDING : 0) | (flat ? EK_SORT_FLAT_INDEX : 0), nullptr, &index);
+        return index;
+    }
+
+private:
+    /// one ek_hip_sort_segments call for the outputs asked for; the checks come before the operands are evaluated and before any call
+    void sort_segments_(const char *who, const HIPArray<uint32_t> &starts, int flags, HIPArray *values, HIPArray<uint32_t> *index) const {
+        static_assert(!IsMask, "segment_sort_(): not defined for masks");
+        if (!&ek_hip_sort_segments)
+            throw std::runtime_error("HIPArray::" + std::string(who) + "(): this C ABI has no entry ek_hip_sort_segments");
+        const size_t n = size(), m = starts.size();
+        if (n > 0xFFFFFFFFull || m > 0xFFFFFFFFull)
+            throw std::runtime_error("HIPArray::" + std::string(who) + "(): " + std::to_string(n) + " entries in " + std::to_string(m) +
+                                     " segments: more than 2^32 - 1 are not supported");
+        if (values) *values = HIPArray();
+        if (index) *index = HIPArray<uint32_t>();
+        if (n == 0) return;
+        if (m) starts.materialize();
+        materialize();
+        if (values) *values = empty_(n);
+        if (index) *index = HIPArray<uint32_t>::empty_(n);
+        detail::hip_check(ek_hip_sort_segments(Type, values ? values->m_buf->ptr : nullptr, index ? (uint32_t *) index->m_buf->ptr : nullptr,
+                                               ptr_(), n, m ? (const uint32_t *) starts.ptr_() : nullptr, m, flags), who);
+    }
+public:
+
     /// Prefix sums inside every block of `block` consecutive entries (ek_hip_psum_blocks): entry k of a block becomes the sum of
     /// its entries 0 .. k, 0 .. k - 1 with `exclusive` (the empty sum is +0), k .. block - 1 with `reverse`.  An unevaluated
     /// operand is evaluated once; a host scalar is an array of one entry.

@@ -770,6 +770,46 @@ EK_API EK_OPTIONAL int ek_hip_search_sorted_segments(int type, uint32_t *out, co
 EK_API EK_OPTIONAL int ek_hip_search_sorted_segments_plan(int type, size_t nt, size_t m, size_t n, int indexed, int compute_units, int *route,
                                                           size_t *tile_needles, size_t *tiles_per_workgroup, size_t *workgroups,
                                                           size_t *lds_entries, size_t *window);
+/* Stable sort inside every ragged segment: the counterpart of ek_hip_sort_blocks for the segments of ek_hip_reduce_segments (starts[m]
+ * := n; segment j is [lo_j, hi_j) with lo_j = min(starts[j], n) and hi_j = max(lo_j, min(starts[j + 1], n))).  With x = in + lo_j
+ * and p the permutation that puts x in order,
+ *     out_index[lo_j + k]  = p[k]  (the segment-local position of the entry that lands at slot k; + lo_j with EK_SORT_FLAT_INDEX:
+ *                                   ready for a gather from another array)
+ *     out_values[lo_j + k] = x[p[k]], the entry's own bits, fetched through the sorted position
+ * -- a ray's hits in depth order once rays keep different counts, and the call that makes the segments ascend that
+ * ek_hip_search_sorted_segments expects (a float CDF from ek_hip_psum_segments need not).  Order, ties, -0.0, NaN and both flags are
+ * those of ek_hip_sort_blocks: per segment numpy.argsort(segment, kind="stable"), descending argsort(-segment) for floating point
+ * and argsort(~segment) for integers, exactly; ek_hip_sort_segments(x, arange(m) * B) is bit-equal to ek_hip_sort_blocks(x, B).
+ * Entries in front of min(starts[0], n) belong to no segment and stay where they are: out_values copies them, out_index holds
+ * their own position i in both modes (this prefix counts from 0); m == 0: the whole array is such a prefix, and starts may be null.
+ * Empty segments own nothing.  Either output pointer may be NULL (not both): that output is neither computed into memory nor
+ * needs a buffer.  I32 .. F64 (EK_BOOL or an unknown type: EK_ERR_UNSUPPORTED); n or m above 2^32 - 1: EK_ERR_UNSUPPORTED; both
+ * outputs NULL, a null `in` or (m > 0) `starts` with n > 0, an unknown flag bit, a pointer that is no multiple of its element size,
+ * or `in` and the outputs (or the two outputs) overlapping: EK_ERR_INVALID, before anything is launched; n == 0: nothing is
+ * launched.  The pointers need only element alignment.  Guarantees:
+ *   - the order is total on (key, input position): bit-identical from run to run;
+ *   - no global atomics, no read-back, no host wait, no kernel waits for another workgroup; the launch sequence is fixed by
+ *     (type, n, m, compute units), so the call is capturable into a step graph and replayable with other contents in `starts`;
+ *     scratch comes from ek_hip_malloc and is freed stream-ordered;
+ *   - `starts` is never validated (that would need a read-back): whatever it holds, every read lies inside in[0 .. n) and
+ *     starts[0 .. m), every entry of each requested output is written, nothing outside them, a flat result lies in [0, n) and so
+ *     does a local one, and every loop's trip count is bounded by a host-known number or the log2 of one.  Where `starts` does not
+ *     ascend only the values are unspecified.
+ * ONE output-driven route: a workgroup owns a run of consecutive tiles of *tile = 2048 entries, marks the starts that fall into a
+ * tile as head flags in LDS and sorts the tile's composites by (run in tile, key, position) in one bitonic network; a segment
+ * inside one tile is final there, the pieces of a segment that crosses a tile boundary go to scratch and are merged by *merges =
+ * ceil(log2(*tiles)) launches, pass p over pairs of groups of 2^p tiles.  A one-workgroup launch in between counts, on the device,
+ * how many passes the data need; the workgroups of every later pass return at once.  ek_hip_sort_segments_plan (host only, no device
+ * access; compute_units == 0: 256; want_index changes nothing today) reports *tile, *tiles = ceil(n / *tile), *tiles_per_workgroup
+ * = ceil(tiles / min(tiles, 8 x compute_units)), *workgroups = ceil(tiles / *tiles_per_workgroup), *merges, *merge_workgroups (the
+ * grid of a merge launch), *launches (1 for one tile, 2 + *merges otherwise) and *scratch_bytes (0 for one tile; else one buffer of
+ * n composites of 8 or 12 bytes, two from two merges on, and tiles + 1 words); all but *tile are 0 for n == 0 or m == 0 (m == 0 is
+ * a copy and a count).  EK_OPTIONAL: enoki/hip.h asks for the entries' addresses first and throws without them. */
+EK_API EK_OPTIONAL int ek_hip_sort_segments(int type, void *out_values, uint32_t *out_index, const void *in, size_t n, const uint32_t *starts,
+                                            size_t m, int flags);
+EK_API EK_OPTIONAL int ek_hip_sort_segments_plan(int type, size_t n, size_t m, int want_index, int compute_units, size_t *tile, size_t *tiles,
+                                                 size_t *tiles_per_workgroup, size_t *workgroups, int *merges, size_t *merge_workgroups,
+                                                 int *launches, size_t *scratch_bytes);
 
 /* Stable sort of (key, element number) pairs by the low `key_bits` bits of 32-bit keys:
  *     keys_out = keys sorted ascending, perm_out[j] = original position of keys_out[j]; equal keys keep their order.
