@@ -29,7 +29,7 @@ COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-math-errno", 
           "-Wall", "-Wno-unused-function", f"-I{os.path.join(ROOT, 'include')}"]
 DEVICE = [f"--offload-arch={ARCH}"]
 
-LIB_SOURCES = ["runtime.cpp", "dist.cpp", "elementwise.hip", "memory.hip", "reduce.hip", "scatter_binned.hip", "random.hip", "gathered.hip", "scan.hip", "bucketed.hip", "bucketed_early.hip", "bucket_refine.hip", "search.hip", "block_reduce.hip", "block_scan.hip", "block_search.hip", "block_sort.hip", "block_segments.hip", "segment_scan.hip", "segment_search.hip", "segment_sort.hip"]
+LIB_SOURCES = ["runtime.cpp", "dist.cpp", "elementwise.hip", "memory.hip", "reduce.hip", "scatter_binned.hip", "random.hip", "gathered.hip", "scan.hip", "bucketed.hip", "bucketed_early.hip", "bucket_refine.hip", "search.hip", "block_reduce.hip", "block_scan.hip", "block_search.hip", "block_sort.hip", "block_segments.hip", "segment_scan.hip", "segment_search.hip", "segment_sort.hip", "sort.hip"]
 # measurement scaffolding (tools/probe_*.py): its own library on top of the public C ABI, never loaded by the product
 PROBE_SOURCES = ["probe.hip", "probe_lds64.hip", "probe_valu.hip", "probe_rt.cpp"]
 

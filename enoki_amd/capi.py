@@ -56,6 +56,7 @@ EXPORTS = [
     "ek_hip_psum_segments", "ek_hip_psum_segments_plan",
     "ek_hip_search_sorted_segments", "ek_hip_search_sorted_segments_plan",
     "ek_hip_sort_segments", "ek_hip_sort_segments_plan",
+    "ek_hip_sort", "ek_hip_sort_plan",
 ]
 
 
@@ -623,6 +624,35 @@ def sort_blocks_plan(dtype, n, block, want_index=True, compute_units=0):
     check(lib.ek_hip_sort_blocks_plan(NP2EK[np.dtype(dtype)], ctypes.c_size_t(n), ctypes.c_size_t(block), int(bool(want_index)),
                                       int(compute_units), ctypes.byref(r), ctypes.byref(t), ctypes.byref(c), ctypes.byref(mp), ctypes.byref(w)))
     return r.value, t.value, c.value, mp.value, w.value
+
+
+SORT_ROUTES = {0: "trivial", 1: "forwarded", 2: "radix"}
+
+
+def sort(a, descending=False, values=True, index=True, out_values=None, out_index=None, flags=None):
+    """stable sort of the whole array `a` (ek_hip_sort): returns (values, index), None for an output that was not asked for.
+    index: uint32, the position in `a` of the entry at each slot.  out_values / out_index: write into these arrays (they must not
+    overlap `a` or each other)"""
+    if values and out_values is None:
+        out_values = Buf(a.dtype, a.n)
+    if index and out_index is None:
+        out_index = Buf(np.uint32, a.n)
+    if flags is None:
+        flags = SORT_DESCENDING if descending else 0
+    check(lib.ek_hip_sort(a.ek, ctypes.c_void_p(out_values.ptr if out_values is not None else None),
+                          ctypes.c_void_p(out_index.ptr if out_index is not None else None),
+                          ctypes.c_void_p(a.ptr if a.n else None), ctypes.c_size_t(a.n), int(flags)))
+    return out_values, out_index
+
+
+def sort_plan(dtype, n, want_index=True, compute_units=0):
+    """(route, passes, tile, tiles_per_workgroup, workgroups, launches, scratch_bytes): what ek_hip_sort does for n entries of `dtype`
+    under the current "sort_radix" tuning (host only).  route: a key of SORT_ROUTES"""
+    r, ps, la = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    t, tw, w, sb = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+    check(lib.ek_hip_sort_plan(NP2EK[np.dtype(dtype)], ctypes.c_size_t(n), int(bool(want_index)), int(compute_units), ctypes.byref(r),
+                               ctypes.byref(ps), ctypes.byref(t), ctypes.byref(tw), ctypes.byref(w), ctypes.byref(la), ctypes.byref(sb)))
+    return r.value, ps.value, t.value, tw.value, w.value, la.value, sb.value
 
 
 SEGMENT_ROUTES = {0: "nothing", 1: "grouped", 2: "segment", 3: "split"}

@@ -33,7 +33,9 @@ template <int ES> __device__ __forceinline__ SortComp<ES> comp_padding() {
     else return SortComp<8>{ ~0ull, ~0u };
 }
 
-template <int ES, int KIND, typename U> __device__ __forceinline__ SortComp<ES> comp_make(U u, uint32_t pos, bool desc) {
+/// the order-preserving unsigned key of an entry's bits (the table at the top); sort.hip's radix passes sort by it byte by byte
+template <int ES, int KIND, typename U> __device__ __forceinline__ U sort_key(U u, bool desc) {
+    static_assert(sizeof(U) == ES, "sort_key(): the bits of one entry");
     constexpr U kSign = U(1) << (ES * 8 - 1), kOnes = ~U(0);
     U key;
     if constexpr (KIND == kSortFloat) {
@@ -49,6 +51,11 @@ template <int ES, int KIND, typename U> __device__ __forceinline__ SortComp<ES> 
         key = KIND == kSortSigned ? U(u ^ kSign) : u;
         if (desc) key = ~key;
     }
+    return key;
+}
+
+template <int ES, int KIND, typename U> __device__ __forceinline__ SortComp<ES> comp_make(U u, uint32_t pos, bool desc) {
+    const U key = sort_key<ES, KIND, U>(u, desc);
     if constexpr (ES == 4) return SortComp<4>{ ((uint64_t) key << 32) | pos };
     else return SortComp<8>{ key, pos };
 }

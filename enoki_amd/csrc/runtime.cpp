@@ -637,6 +637,7 @@ int ek_hip_set_tuning(const char *key, int value) {
     else if (!strcmp(key, "early_adjoint") && (value == 0 || value == 1)) t.early_adjoint = value;
     else if (!strcmp(key, "partition_cache") && (value == 0 || value == 1)) t.partition_cache = value;
     else if (!strcmp(key, "partition_refine") && value >= 0 && value <= 2) t.partition_refine = value;
+    else if (!strcmp(key, "sort_radix") && value >= 0 && value <= 2) t.sort_radix = value;
     else if (!strcmp(key, "xcd_balance") && value >= 0 && value <= 2) t.xcd_balance = value;
     else return fail(EK_ERR_INVALID, "ek_hip_set_tuning(): unknown key/value %s=%d", key, value);
     return EK_OK;

@@ -272,6 +272,16 @@ template <typename Array> py::class_<Array> bind_array(py::module_ &m, const cha
               "array"_a, "block"_a, "descending"_a = false, "flat"_a = false,
               "The permutation of block_sort as UInt32: per output slot the row-local position 0 .. block - 1 of the entry that lands "
               "there; with flat=True its position in the flat array (row * block + local), ready for gather(other, p).  No gradient.");
+        // stable sort of the whole array; sort is differentiable, argsort returns UInt32 and has no gradient
+        m.def("sort", [](const Array &a, bool descending) { return enoki::sort(a, descending); }, "array"_a, "descending"_a = false,
+              "Stable sort of the whole array: ascending by <, with descending by >; equal entries keep their input order, -0.0 == +0.0, "
+              "every NaN comes last in both directions; the values are the entries' own bits.  The order of numpy.argsort(array, "
+              "kind='stable'); bit for bit block_sort(array, len(array)), by radix passes for long arrays.  Differentiable: the adjoint "
+              "is a scatter through the permutation.");
+        m.def("argsort", [](const Array &a, bool descending) { return enoki::argsort(a, descending); }, "array"_a, "descending"_a = false,
+              "The permutation of sort as UInt32: per output slot the position of the entry that lands there, so that gather(other, "
+              "argsort(keys)) reorders another array along.  With p = argsort(ids), search_sorted(gather(ids, p), arange(m)) gives the "
+              "starts of the groups for the segment_* calls.  No gradient.");
         // one value per ragged segment (starts: UInt32, non-decreasing, starts[m] := len(array)), and the transpose; segment_sum
         // and segment_repeat are differentiable, starts carries no gradient
         using Starts = uint32_array_t<Array>;

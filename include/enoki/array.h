@@ -1730,6 +1730,31 @@ template <typename T> inline auto block_argsort(const T &x, size_t block, bool d
     else throw std::runtime_error("block_argsort(): not available for this array type");
 }
 
+/// Stable sort of a WHOLE flat array, in block_sort's order: sort(x) == block_sort(x, size(x)) and argsort(x) ==
+/// block_argsort(x, size(x)) bit for bit -- numpy.argsort(x, kind="stable"), with `descending` argsort(-x) for floating point and
+/// argsort(~x) for integers; ties keep their input order, -0.0 == +0.0, every NaN comes last in both directions, the values are the
+/// entries' own bits.  argsort is the call that makes the entries of a ray, pixel or cell consecutive: with p = argsort(ids),
+/// gather(payload, p) is grouped, and search_sorted(gather(ids, p), arange(m)) gives the `starts` that the segment_* calls take.
+/// One call each (least-significant-digit radix passes for long arrays, block_sort's route for short ones), bit-identical from run
+/// to run; sort is differentiable (its adjoint is a scatter through the permutation), argsort has no gradient.  Both take enoki
+/// arrays of depth 1 ONLY and drop out of overload resolution for anything else: an unqualified sort(first, last, cmp) over a
+/// container of arrays, which finds this namespace through its arguments, still means std::sort.  A flat array type without the
+/// members throws at run time.
+namespace detail {
+    template <typename T, typename = void> struct has_sort : std::false_type { };
+    template <typename T> struct has_sort<T, std::void_t<decltype(std::declval<const T &>().sort_(false))>> : std::true_type { };
+    template <typename T, typename = void> struct has_argsort : std::false_type { };
+    template <typename T> struct has_argsort<T, std::void_t<decltype(std::declval<const T &>().argsort_(false))>> : std::true_type { };
+}
+template <typename T, std::enable_if_t<is_array_v<T> && array_depth_v<T> == 1, int> = 0> inline T sort(const T &x, bool descending = false) {
+    if constexpr (detail::has_sort<T>::value) return x.sort_(descending);
+    else throw std::runtime_error("sort(): not available for this array type");
+}
+template <typename T, std::enable_if_t<is_array_v<T> && array_depth_v<T> == 1, int> = 0> inline auto argsort(const T &x, bool descending = false) {
+    if constexpr (detail::has_argsort<T>::value) return uint32_array_t<T>(x.argsort_(descending));
+    else throw std::runtime_error("argsort(): not available for this array type");
+}
+
 /// One value per RAGGED segment of a flat array: `starts` is a UInt32 array of m non-decreasing positions, starts[m] := n = size(x),
 /// and segment_sum(x, starts)[j] = x[min(starts[j], n)] + .. + x[min(starts[j + 1], n) - 1], likewise segment_prod / segment_min /
 /// segment_max; an empty segment yields +0 / 1 / NaN (the type's max / lowest for integers).  The starts of given counts are

@@ -825,6 +825,23 @@ template <typename Type_> struct DiffArray : ArrayTag {
         return ReplaceScalar<uint32_t>(block_argsort(m_value, block, descending, flat));
     }
 
+    /// Stable sort of the whole array: a tracked source asks the one sorting call for the permutation as well and records
+    /// block_sort's tape node, which keeps it (Tape::append_block_sort: forward gathers through the permutation, backward scatters
+    /// into zeros); an untracked source sorts values only
+    DiffArray sort_(bool descending) const {
+        if constexpr (Enabled && detail::has_sort<Type>::value) {
+            if (m_index) {
+                uint32_array_t<Type> perm;
+                Type result = m_value.sort_(descending, &perm);
+                return create(tape()->append_block_sort(m_index, perm), std::move(result));
+            }
+        }
+        return create(0, sort(m_value, descending));
+    }
+
+    /// The permutation is piecewise constant in the entries: computed on the detached values, no node, no edges
+    ReplaceScalar<uint32_t> argsort_(bool descending) const { return ReplaceScalar<uint32_t>(argsort(m_value, descending)); }
+
     DiffArray block_prod_(size_t block) const {
         if (Enabled && m_index != 0) throw std::runtime_error("DiffArray::block_prod_(): gradients not implemented");
         return create(0, block_prod(m_value, block));

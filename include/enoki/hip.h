@@ -2023,6 +2023,44 @@ private:
     }
 public:
 
+    /// Stable sort of the whole array (ek_hip_sort): the order of block_sort_ -- ascending by `<`, by `>` with `descending`; equal
+    /// entries keep their input order, -0.0 == +0.0, every NaN comes last; the entries' own bits.  With `perm` the same call also
+    /// writes the permutation: result == gather(*this, *perm).  An unevaluated operand is evaluated once; a host scalar is an array
+    /// of one entry; no entries make no call.
+    HIPArray sort_(bool descending, HIPArray<uint32_t> *perm = nullptr) const {
+        HIPArray values;
+        sort_all_("sort_", descending, &values, perm);
+        return values;
+    }
+
+    /// ... and the permutation alone: per output slot the position of the entry that lands there, ready for gather(other, p).  No
+    /// values are written.
+    HIPArray<uint32_t> argsort_(bool descending) const {
+        HIPArray<uint32_t> index;
+        sort_all_("argsort_", descending, nullptr, &index);
+        return index;
+    }
+
+private:
+    /// one ek_hip_sort call for the outputs asked for; the checks come before the operand is evaluated and before any call
+    void sort_all_(const char *who, bool descending, HIPArray *values, HIPArray<uint32_t> *index) const {
+        static_assert(!IsMask, "sort_(): not defined for masks");
+        const size_t n = size();
+        if (n > 0xFFFFFFFFull)
+            throw std::runtime_error("HIPArray::" + std::string(who) + "(): " + std::to_string(n) + " entries, more than 2^32 - 1, are not supported");
+        if (!&ek_hip_sort)
+            throw std::runtime_error("HIPArray::" + std::string(who) + "(): this C ABI has no entry ek_hip_sort");
+        if (values) *values = HIPArray();
+        if (index) *index = HIPArray<uint32_t>();
+        if (n == 0) return;
+        materialize();
+        if (values) *values = empty_(n);
+        if (index) *index = HIPArray<uint32_t>::empty_(n);
+        detail::hip_check(ek_hip_sort(Type, values ? values->m_buf->ptr : nullptr, index ? (uint32_t *) index->m_buf->ptr : nullptr, ptr_(), n,
+                                      descending ? EK_SORT_DESCENDING : 0), who);
+    }
+public:
+
     // -----------------------------------------------------------------------------------------
     //  Storage access
     // -----------------------------------------------------------------------------------------

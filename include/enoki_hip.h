@@ -167,7 +167,7 @@ EK_API int ek_hip_graph_end(ek_hip_graph **out);
 EK_API int ek_hip_graph_launch(ek_hip_graph *graph);
 EK_API uint64_t ek_hip_graph_launch_count(const ek_hip_graph *graph);   /* kernel launches inside one replay */
 EK_API int ek_hip_graph_destroy(ek_hip_graph *graph);
-EK_API int ek_hip_set_tuning(const char *key, int value);   /* "reduce_blocks_per_cu", "scatter_add_binned", "deterministic", "gather_records", "bucket_ordered", "early_adjoint", "partition_cache", "partition_refine" (0 never, 1 automatic, 2 whenever the shape is covered) */
+EK_API int ek_hip_set_tuning(const char *key, int value);   /* "reduce_blocks_per_cu", "scatter_add_binned", "deterministic", "gather_records", "bucket_ordered", "early_adjoint", "partition_cache", "partition_refine" (0 never, 1 automatic, 2 whenever the shape is covered), "sort_radix" (ek_hip_sort: 0 never the radix route, 1 automatic, 2 for every n >= 2) */
 /* Per-kernel timing: between begin and end one HIP event is recorded on the library stream after every
    launch.  ek_hip_profile_end() synchronizes and returns a malloc'd JSON array (caller free()s) of
    {"kernel", "launches", "total_ms", "bytes", "elements"}; `bytes` are the ALGORITHMIC bytes of the
@@ -810,6 +810,33 @@ EK_API EK_OPTIONAL int ek_hip_sort_segments(int type, void *out_values, uint32_t
 EK_API EK_OPTIONAL int ek_hip_sort_segments_plan(int type, size_t n, size_t m, int want_index, int compute_units, size_t *tile, size_t *tiles,
                                                  size_t *tiles_per_workgroup, size_t *workgroups, int *merges, size_t *merge_workgroups,
                                                  int *launches, size_t *scratch_bytes);
+/* Stable sort of a whole array: with p the permutation that puts the n entries of `in` in order,
+ *     out_index[k]  = p[k]  (the position of the entry that lands at slot k: ready for a gather from another array)
+ *     out_values[k] = in[p[k]], the entry's own bits, fetched through the sorted position
+ * -- the call that makes the hits of a ray, the fragments of a pixel or the particles of a cell consecutive, as every *_blocks and
+ * *_segments entry presumes: sort the ids, gather the payload through out_index, and ek_hip_search_sorted(sorted ids, 0 .. m - 1)
+ * gives the `starts` of the segments.  Order, ties, -0.0, NaN and EK_SORT_DESCENDING are those of ek_hip_sort_blocks, and the result
+ * is bit for bit that of ek_hip_sort_blocks(.., n, block = n, flags): numpy.argsort(x, kind="stable"), descending argsort(-x) for
+ * floating point and argsort(~x) for integers.  EK_SORT_FLAT_INDEX is accepted and changes nothing.  Either output pointer may be
+ * NULL (not both): that output is neither written nor allocated.  I32 .. F64 (EK_BOOL: EK_ERR_UNSUPPORTED); more than 2^32 - 1
+ * entries: EK_ERR_UNSUPPORTED; an unknown flag bit, a null `in` with n > 0, a misaligned pointer, `in` overlapping an output or the
+ * outputs overlapping each other: EK_ERR_INVALID, all before any launch; n == 0 launches nothing.
+ * Guarantees: the order is total on (key, position), so the result is bit-identical from run to run; no global atomics; no kernel
+ * waits for another workgroup (no look-back, no ticket); no read-back and no host wait; the launch sequence is fixed by (type, n,
+ * compute units, tuning), so the call can be captured into a step graph and replayed with other contents; scratch comes from
+ * ek_hip_malloc and is freed stream-ordered.
+ * ek_hip_sort_plan (host only, no device access; compute_units == 0: 256; want_index changes nothing) reports *route: 0 trivial
+ * (n <= 1), 1 forwarded to ek_hip_sort_blocks with block == n, 2 radix: *passes = 4 or 8 (the key bytes) least-significant-digit
+ * passes of 8 bits over (key, position) pairs, each a per-workgroup digit count, two scans of the counts and a stable scatter that
+ * ranks with wave ballots; *tile entries per tile (route 1: block_sort's chunk), *tiles_per_workgroup = ceil(tiles / min(tiles,
+ * 2 x compute_units)) with tiles = ceil(n / *tile), *workgroups = ceil(tiles / *tiles_per_workgroup) (route 1: the grid of the first
+ * launch), *launches (route 2: 4 x *passes; route 1: those of ek_hip_sort_blocks) and *scratch_bytes.  The tuning "sort_radix"
+ * (ek_hip_set_tuning) picks between routes 1 and 2: 0 always forwards, 1 (default) takes the radix route from the measured crossover
+ * on -- one threshold per element size, never below block_sort's chunk + 1 --, 2 takes it for every n >= 2; the plan reports the
+ * route under the current setting.  EK_OPTIONAL: enoki/hip.h asks for the entry's address first and throws without it. */
+EK_API EK_OPTIONAL int ek_hip_sort(int type, void *out_values, uint32_t *out_index, const void *in, size_t n, int flags);
+EK_API EK_OPTIONAL int ek_hip_sort_plan(int type, size_t n, int want_index, int compute_units, int *route, int *passes, size_t *tile,
+                                        size_t *tiles_per_workgroup, size_t *workgroups, int *launches, size_t *scratch_bytes);
 
 /* Stable sort of (key, element number) pairs by the low `key_bits` bits of 32-bit keys:
  *     keys_out = keys sorted ascending, perm_out[j] = original position of keys_out[j]; equal keys keep their order.
