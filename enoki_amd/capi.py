@@ -46,7 +46,7 @@ EXPORTS = [
     "ek_hip_graph_launch_count", "ek_hip_graph_destroy", "ek_hip_sort_pairs", "ek_hip_reduce_map", "ek_hip_reduce_chain", "ek_hip_map_chain", "ek_hip_map_chain_product", "ek_hip_partition_class_state", "ek_hip_scatter_add_multi_map", "ek_hip_binding_slot",
     "ek_hip_dist_unique_id", "ek_hip_dist_init", "ek_hip_dist_world", "ek_hip_dist_shard_range", "ek_hip_dist_all_reduce",
     "ek_hip_dist_reduce_scatter", "ek_hip_dist_all_gather", "ek_hip_dist_finalize", "ek_hip_dist_rccl_path",
-    "ek_hip_bucketed_applicable", "ek_hip_bucketed_pair_create", "ek_hip_bucketed_pair_create_hinted", "ek_hip_bucketed_pair_create_masked", "ek_hip_bucketed_pair_create_scalar", "ek_hip_bucketed_pair_create_scalar_device", "ek_hip_bucketed_addend_adjoint", "ek_hip_bucketed_reduce", "ek_hip_bucketed_scatter_add", "ek_hip_bucketed_scatter_add_scaled", "ek_hip_bucketed_early_pair",
+    "ek_hip_bucketed_applicable", "ek_hip_bucketed_pair_create", "ek_hip_bucketed_pair_create_hinted", "ek_hip_bucketed_pair_create_masked", "ek_hip_bucketed_pair_create_scalar", "ek_hip_bucketed_pair_create_scalar_device", "ek_hip_bucketed_addend_adjoint", "ek_hip_bucketed_reduce", "ek_hip_bucketed_scatter_add", "ek_hip_bucketed_scatter_add_scaled", "ek_hip_bucketed_early_pair", "ek_hip_bucketed_take_tables",
     "ek_hip_bucketed_piece_counts", "ek_hip_bucketed_destroy", "ek_hip_bucketed_partition_retain", "ek_hip_bucket_partition_release", "ek_hip_bucketed_pair_create_on", "ek_hip_index_partition_create", "ek_hip_index_partition_get", "ek_hip_index_partition_destroy", "ek_hip_gather_address",
     "ek_hip_search_sorted", "ek_hip_search_sorted_plan", "ek_hip_search_sorted_blocks", "ek_hip_search_sorted_blocks_plan",
     "ek_hip_reduce_blocks", "ek_hip_reduce_blocks_plan", "ek_hip_repeat",
@@ -846,6 +846,21 @@ class Bucketed:
             check(lib.ek_hip_bucketed_scatter_add_scaled(self.handle, count, bases, from_u, ops, imm, wt, fr, sc))
         else:
             check(lib.ek_hip_bucketed_scatter_add(self.handle, count, bases, from_u, ops, imm, wt, fr))
+
+    def take_tables(self, streams, scales=None):
+        """ek_hip_bucketed_take_tables: the direct tables of the streams (as in scatter_add) as owned Bufs of K elements, or None when
+        the library answers EK_ERR_UNSUPPORTED (the caller folds with scatter_add as before)"""
+        count = len(streams)
+        from_u = (ctypes.c_int * count)(*[0 if s[0] is None else 1 for s in streams])
+        ops = (ctypes.c_int * count)(*[UNARY[s[0] or "copy"] for s in streams])
+        wt = (ctypes.c_int * count)(*[int(bool(s[2])) for s in streams])
+        sc = (ctypes.c_uint64 * count)(*[_imm_bits(v, self.dtype) for v in scales]) if scales is not None else None
+        out = (ctypes.c_void_p * count)()
+        rc = lib.ek_hip_bucketed_take_tables(self.handle, count, from_u, ops, wt, sc, out)
+        if rc == -2:          # EK_ERR_UNSUPPORTED
+            return None
+        check(rc)
+        return [Buf(self.dtype, self.K, ptr=out[s]) for s in range(count)]
 
     def piece_counts(self):
         """(pieces that exist, most pieces of any one bucket) -- ek_hip_bucketed_piece_counts; synchronises"""

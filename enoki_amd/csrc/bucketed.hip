@@ -494,7 +494,7 @@ Bucketed::~Bucketed() {
         meta = nullptr;
     }
     if (meta_borrowed) meta = nullptr;
-    for (void *p : { meta, early, page_lists })
+    for (void *p : { meta, early, page_lists, direct[0], direct[1] })     // (direct tables that nobody took; the mode words live in direct[0]'s block)
         if (p) ek_hip_free(p);
     if (!owner)
         for (void *p : { pair_idx, x_b, u_b, m_b })
@@ -957,12 +957,14 @@ template <int C>
 __global__ __launch_bounds__(256) void k_fold_fixed_pieces(FoldTargets<float, C> targets, const long long *__restrict__ partials,
                                                            const uint32_t *__restrict__ piece_mode, const uint32_t *__restrict__ piece_prefix,
                                                            size_t table_size, size_t partial_stride, unsigned fresh, int shift,
-                                                           const uint32_t *__restrict__ xmax_bits, int S0, int first_table) {
+                                                           const uint32_t *__restrict__ xmax_bits, int S0, int first_table,
+                                                           const float *__restrict__ direct0, const float *__restrict__ direct1) {
     const size_t k0 = ((size_t) blockIdx.x * 256 + threadIdx.x) * kFoldPerLane;
     if (k0 >= table_size) return;
     const int c = first_table + (int) blockIdx.y;                 // 0: the plain sums, 1: the x-weighted sums
     float *__restrict__ target = targets.table[blockIdx.y];
-    partials += (size_t) c * partial_stride;
+    const bool direct = direct0 || direct1;                       // (one of the two may have left: ek_hip_bucketed_take_tables)
+    if (!direct) partials += (size_t) c * partial_stride;
     const uint32_t b = (uint32_t) (k0 >> shift), local = (uint32_t) (k0 & (((size_t) 1 << shift) - 1));
     const bool is_fresh = (fresh >> blockIdx.y) & 1u;
     const uint32_t p0 = piece_prefix[b], p1 = piece_prefix[b + 1];
@@ -978,7 +980,14 @@ __global__ __launch_bounds__(256) void k_fold_fixed_pieces(FoldTargets<float, C>
         for (int j = 0; j < kFoldPerLane; ++j) if (j < lim) old[j] = target[k0 + j];
     }
     const uint32_t xm = xmax_bits[0];
-    if (p1 - p0 == 1u) {
+    if (direct) {
+        // DIRECT tables (every bucket one piece; `partials` is null): plane c is a table of its own, the slot of bucket b its floats at
+        // plane + b * Bins -- entry k0 at plane + k0.  (The kernel finished them as for a fresh table at scale 1: 0 + (0 * back + sum),
+        // which the statements below leave as they are before the factor and the old value are applied.)
+        const float *slotf = (c ? direct1 : direct0) + ((size_t) b << shift);
+#pragma unroll
+        for (int j = 0; j < kFoldPerLane; ++j) if (j < lim) fsum[j] = __builtin_nontemporal_load(slotf + local + j);
+    } else if (p1 - p0 == 1u) {
         // a bucket that is one piece wrote floats whatever it ran under (bucketed_early.hip): no mode to wait for, a quarter of the bytes
         const float *slotf = reinterpret_cast<const float *>(partials + ((size_t) p0 << shift));
 #pragma unroll
@@ -1199,6 +1208,9 @@ static int bucketed_scatter_add(Bucketed *b, int count, void *const *bases, cons
         for (int s = 0; s < count; ++s)
             match = match && from_u[s] && (map_ops ? map_ops[s] : (int) EK_COPY) == b->early_op;
         if (count == 2) match = match && (weighted[0] != 0) != (weighted[1] != 0);
+        // (direct tables: a plane that a gradient array took over -- ek_hip_bucketed_take_tables -- is no longer here to be folded)
+        if (b->early_direct)
+            for (int s = 0; s < count; ++s) match = match && b->direct[weighted[s] ? 1 : 0] != nullptr;
         if (match) {
             Context &c = ctx();
             const size_t stride = (size_t) b->max_pieces * b->bins();
@@ -1206,6 +1218,10 @@ static int bucketed_scatter_add(Bucketed *b, int count, void *const *bases, cons
             if constexpr (std::is_same_v<T, float>) {
                 if (b->early_fixed) {
                     const uint32_t *xmax = b->active + (kPgMetaResultXmax - kPgMetaResult);
+                    // (direct tables -- a factor other than 1, a target that holds data, one fresh target of two: the same fold reads them)
+                    const long long *slots = b->early_direct ? nullptr : (const long long *) b->early;
+                    const float *direct0 = b->early_direct ? (const float *) b->direct[0] : nullptr;
+                    const float *direct1 = b->early_direct ? (const float *) b->direct[1] : nullptr;
                     if (count == 2) {
                         const int s_plain = weighted[0] ? 1 : 0, s_weighted = 1 - s_plain;
                         FoldTargets<float, 2> targets;
@@ -1214,19 +1230,19 @@ static int bucketed_scatter_add(Bucketed *b, int count, void *const *bases, cons
                         targets.scale[0] = scale[s_plain];
                         targets.scale[1] = scale[s_weighted];
                         const unsigned fr = fresh ? ((fresh[s_plain] ? 1u : 0u) | (fresh[s_weighted] ? 2u : 0u)) : 0u;
-                        hipLaunchKernelGGL((k_fold_fixed_pieces<2>), dim3(grid, 2), dim3(256), 0, c.stream, targets, (const long long *) b->early,
+                        hipLaunchKernelGGL((k_fold_fixed_pieces<2>), dim3(grid, 2), dim3(256), 0, c.stream, targets, slots,
                                            (const uint32_t *) b->early_modes, (const uint32_t *) b->piece_prefix, b->table_size, stride, fr, b->shift,
-                                           xmax, b->early_S0, 0);
+                                           xmax, b->early_S0, 0, direct0, direct1);
                     } else {
                         FoldTargets<float, 1> targets;
                         targets.table[0] = (float *) bases[0];
                         targets.scale[0] = scale[0];
-                        hipLaunchKernelGGL((k_fold_fixed_pieces<1>), dim3(grid, 1), dim3(256), 0, c.stream, targets, (const long long *) b->early,
+                        hipLaunchKernelGGL((k_fold_fixed_pieces<1>), dim3(grid, 1), dim3(256), 0, c.stream, targets, slots,
                                            (const uint32_t *) b->early_modes, (const uint32_t *) b->piece_prefix, b->table_size, stride,
-                                           (fresh && fresh[0]) ? 1u : 0u, b->shift, xmax, b->early_S0, weighted[0] ? 1 : 0);
+                                           (fresh && fresh[0]) ? 1u : 0u, b->shift, xmax, b->early_S0, weighted[0] ? 1 : 0, direct0, direct1);
                     }
                     EK_LAUNCH_CHECK("scatter_add_fold", (size_t) count * b->table_size,
-                                    (size_t) count * (stride * sizeof(long long) + 2 * b->table_size * sizeof(T)));
+                                    (size_t) count * ((b->early_direct ? b->table_size * sizeof(T) : stride * sizeof(long long)) + 2 * b->table_size * sizeof(T)));
                     return EK_OK;
                 }
             }
@@ -1846,6 +1862,7 @@ int ek_hip_bucketed_pair_create_scalar_device(int type, int index_type, int op, 
     if (rc == EK_OK) rc = bucketed_pair_create(type, index_type, op, table_a, table, nullptr, table_size, x, index, nullptr, n, hints, out, EK_ERR_INVALID);
     if (rc != EK_OK) { ek_hip_free(table); return rc; }
     (*out)->addend_table = table;
+    (*out)->addend_broadcast = true;
     return EK_OK;
 }
 
@@ -1923,6 +1940,7 @@ int ek_hip_bucketed_pair_create_on(ek_hip_bucket_partition *p, int type, int ind
     b->n = n; b->table_size = table_size;
     b->table_a = table_a; b->table_c = table ? table : table_c;
     b->addend_table = table;
+    b->addend_broadcast = table != nullptr;
     if (addend_bits) { b->scalar_addend = true; b->addend_bits = *addend_bits; }
     b->shift = p->shift; b->has_mask = p->has_mask;
     b->n_buckets = p->n_buckets; b->page_shift = p->page_shift; b->max_pieces = p->max_pieces; b->positions = p->positions;
@@ -1975,6 +1993,33 @@ int ek_hip_bucketed_scatter_add(ek_hip_bucketed *b, int count, void *const *base
 }
 
 int ek_hip_bucketed_early_pair(int map_op, int keep_op) { return early_pair_supported(map_op, keep_op) ? 1 : 0; }
+
+int ek_hip_bucketed_take_tables(ek_hip_bucketed *b, int count, const int *from_u, const int *map_ops, const int *weighted,
+                                const uint64_t *scale_bits, void **tables) {
+    if (!b || !from_u || !weighted || !tables || count < 1) return fail(EK_ERR_INVALID, "ek_hip_bucketed_take_tables(): bad arguments");
+    // the object holds direct tables, and the streams are exactly the early ones (the match of bucketed_scatter_add), unscaled
+    if (count > 2 || !b->slices.empty() || b->type != EK_F32 || !b->has_early || !b->early_direct) return EK_ERR_UNSUPPORTED;
+    for (int s = 0; s < count; ++s) {
+        if (!from_u[s] || (map_ops ? map_ops[s] : (int) EK_COPY) != b->early_op) return EK_ERR_UNSUPPORTED;
+        if (scale_bits && (uint32_t) scale_bits[s] != 0x3F800000u) return EK_ERR_UNSUPPORTED;
+        if (!b->direct[weighted[s] ? 1 : 0]) return EK_ERR_UNSUPPORTED;
+    }
+    if (count == 2 && (weighted[0] != 0) == (weighted[1] != 0)) return EK_ERR_UNSUPPORTED;
+    for (int s = 0; s < count; ++s) {
+        void *&plane = b->direct[weighted[s] ? 1 : 0];
+        tables[s] = plane;             // the caller's from here on (ek_hip_free)
+        plane = nullptr;
+    }
+    if (!b->direct[0]) b->direct_modes = nullptr;          // (they went with plane 0's block)
+    // the sums have left: a second request for them is an unmatched one (the streams are evaluated on the lists), the next forward +
+    // adjoint launch of this object allocates new tables.  A plane that was not asked for (count 1) stays: a later request for IT is
+    // still answered from it, by a take or by the fold -- the bits of the path without direct tables.
+    if (!b->direct[0] && !b->direct[1]) {
+        b->has_early = false;
+        b->early_direct = false;
+    }
+    return EK_OK;
+}
 
 int ek_hip_bucketed_scatter_add_scaled(ek_hip_bucketed *b, int count, void *const *bases, const int *from_u, const int *map_ops,
                                        const uint64_t *imm_bits, const int *weighted, const int *fresh, const uint64_t *scale_bits) {

@@ -518,7 +518,8 @@ __device__ __forceinline__ void bucket_pair_forward_adjoint(T *__restrict__ part
                                                             const BucketLists &bl, int map_op, int keep_op, int shift,
                                                             const BucketFinish<T> &fin, const int zero_op, const T zero_u,
                                                             const uint32_t *__restrict__ xmax_bits, int S0,
-                                                            uint32_t *__restrict__ piece_mode, const RefinedArg<Refined> &refined) {
+                                                            uint32_t *__restrict__ piece_mode, const RefinedArg<Refined> &refined,
+                                                            T *__restrict__ direct1) {
     static_assert(!Refined || (Fixed && sizeof(T) == 4), "the refined stream feeds the fixed-point walk only");
     extern __shared__ __align__(16) unsigned char lds_dynamic[];
     // Fixed: a STATIC block (records of 4 Ki entries + 4 Ki pairs of sums, whatever Bins is) -- its address is a constant of the
@@ -705,6 +706,40 @@ __device__ __forceinline__ void bucket_pair_forward_adjoint(T *__restrict__ part
         }
     }
     if constexpr (Fixed) bucket_finish_fixed_begin(iv, v, partials, fin.ticket, &s_last_fixed);
+    // DIRECT tables (direct1 set: the host knows that every bucket is ONE piece -- this workgroup holds its bucket's final sums): plane c
+    // goes to entries [bucket * Bins, ..) of a table of table_size floats -- plane 0 is table_partials itself, plane 1 is direct1 -- with
+    // the bits k_fold_fixed_pieces writes into a fresh table at scale 1 from this piece's slot, statement for statement: the slot's float
+    // (fsum), no fixed-point piece in front of it (the integer 0, converted, times the fold's `back`), added to the fresh table's 0
+    // (a sum of -0.0 leaves as +0.0).  The last bucket of a table that is no multiple of Bins ends at table_size.
+    [[maybe_unused]] bool direct = false;
+    if constexpr (Fixed) direct = direct1 != nullptr;
+    if (direct) {
+        if constexpr (Fixed) {
+            const size_t first = (size_t) bucket * Bins;
+            const int lim = first < table_size ? (int) (table_size - first < (size_t) Bins ? table_size - first : (size_t) Bins) : 0;
+            const uint32_t xm_fold = (uint32_t) __builtin_amdgcn_readfirstlane((int) xm_early);
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                float *plane = (c ? direct1 : table_partials) + first;
+                const float back = fixed_scale(S0, xm_fold, c == 1).back;        // (the fold's own; a piece under locks has no fixed0 / fixed1)
+                if (!locks) {
+                    const long long *sums = reinterpret_cast<const long long *>(lds_raw + (c + 1) * kFixedRecBytes);
+                    const float own = c ? fixed1.back : fixed0.back;
+                    for (int j = threadIdx.x; j < lim; j += kBucketThreads) {
+                        const float fsum = (float) sums[j] * own;                 // what a one-piece bucket writes into its slot
+                        const float v = (float) (long long) 0ull * back + fsum;
+                        plane[j] = 0.f + v;
+                    }
+                } else {
+                    for (int j = threadIdx.x; j < lim; j += kBucketThreads) {
+                        const float fsum = tables[2 * j + c];
+                        const float v = (float) (long long) 0ull * back + fsum;
+                        plane[j] = 0.f + v;
+                    }
+                }
+            }
+        }
+    } else
     // table c (0: sum of the kept function, 1: sum of x * kept function) of this piece at table_partials + (c * gridDim.x + piece) * Bins
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
@@ -773,9 +808,11 @@ __global__ __launch_bounds__(kBucketThreads) void k_bucket_pair_forward_adjoint(
                                                                                 const T *__restrict__ x_b, BucketLists bl,
                                                                                 int map_op, int keep_op, int shift, BucketFinish<T> fin,
                                                                                 const uint32_t *__restrict__ xmax_bits, int S0,
-                                                                                uint32_t *__restrict__ piece_mode, RefinedArg<Refined> refined) {
+                                                                                uint32_t *__restrict__ piece_mode, RefinedArg<Refined> refined,
+                                                                                T *__restrict__ direct1) {
     bucket_pair_forward_adjoint<T, V, PS, Fixed, Two, Refined>(partials, table_partials, table_a, table_c, T(-0.0), table_size, flip_a, flip_c, pair_idx,
-                                                               x_b, bl, map_op, keep_op, shift, fin, fin.zero_op, T(0), xmax_bits, S0, piece_mode, refined);
+                                                               x_b, bl, map_op, keep_op, shift, fin, fin.zero_op, T(0), xmax_bits, S0, piece_mode, refined,
+                                                               direct1);
 }
 
 // A host-scalar addend (no addend table): the scalar and the dropped lanes' u are kernel arguments.  The fixed-point instantiations
@@ -792,7 +829,22 @@ __global__ __launch_bounds__(kBucketThreads) void k_bucket_pair_forward_adjoint_
                                                                                        const uint32_t *__restrict__ xmax_bits, int S0,
                                                                                        uint32_t *__restrict__ piece_mode, RefinedArg<Refined> refined) {
     bucket_pair_forward_adjoint<T, V, PS, Fixed, Two, Refined>(partials, table_partials, table_a, nullptr, addend, table_size, flips & 1, flips & 2, pair_idx,
-                                                               x_b, bl, map_op, keep_op, shift, fin, map_op, fin.zero_u, xmax_bits, S0, piece_mode, refined);
+                                                               x_b, bl, map_op, keep_op, shift, fin, map_op, fin.zero_u, xmax_bits, S0, piece_mode, refined,
+                                                               nullptr /* slots: ek_hip_bucketed_addend_adjoint reads plane 0 of them */);
+}
+
+/// Is every bucket of the partition exactly ONE piece?  Decided once per kept partition, outside a capture: the piece prefix is read
+/// back (one synchronisation, ~1 KB).  A bucket without a piece -- no lookup fell into it -- makes the answer "no": nobody would write
+/// its range of a direct table, and the fold writes a fresh table's zeros there as it always did.
+static int partition_one_piece(BucketPartition *p) {
+    if (!p->piece_prefix || p->n_buckets <= 0) { p->one_piece_state = -1; return EK_OK; }
+    std::vector<uint32_t> prefix((size_t) p->n_buckets + 1, 0u);
+    EK_HIP_CHECK(hipMemcpyAsync(prefix.data(), p->piece_prefix, prefix.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx().stream));
+    EK_HIP_CHECK(hipStreamSynchronize(ctx().stream));
+    bool one = true;
+    for (int k = 0; k < p->n_buckets; ++k) one = one && prefix[(size_t) k + 1] - prefix[(size_t) k] == 1u;
+    p->one_piece_state = one ? 1 : -1;
+    return EK_OK;
 }
 
 template <typename T>
@@ -808,18 +860,44 @@ int bucketed_forward_adjoint_launch(Bucketed *b, void *out, int map_op, int keep
     const bool bounded = (map_op == EK_SIN || map_op == EK_COS) && (keep_op == EK_SIN || keep_op == EK_COS);
     const bool fixed = sizeof(T) == 4 && early_fixed_enabled() && bounded && b->page_shift != 0 && b->active && Bins * 8 <= kFixedRecBytes;
     const size_t slot = fixed ? sizeof(long long) : sizeof(T);            // bytes per entry of a piece's partial table
-    if (!b->early)
+    const bool scalar = b->scalar_addend;
+    const bool eager = refuse_while_capturing_quiet() == EK_OK;
+    // DIRECT tables: on a kept partition whose buckets are one piece each (asked once per partition, here) the fixed-point kernel
+    // writes the two planes in table layout into two allocations of table_size floats, which a fresh gradient array takes over as they
+    // are (ek_hip_bucketed_take_tables) -- no slots, no fold.  Not for a scalar addend (host or device: its adjoint reads plane 0 of the
+    // slots), not under capture.
+    bool direct = false;
+    if constexpr (sizeof(T) == 4) {
+        const int mode = c.tuning.direct_tables;
+        if (fixed && eager && !scalar && !b->addend_broadcast && b->part && b->stands_on_kept &&
+            (mode == 2 || (mode == 1 && b->table_size >= kDirectTablesMinEntries))) {
+            if (b->part->one_piece_state == 0)
+                if (int rc = partition_one_piece(b->part)) return rc;
+            direct = b->part->one_piece_state == 1;
+        }
+    }
+    if (direct) {
+        // (the mode words the kernel writes and nobody reads here go BEHIND plane 0, in the same block: no allocation of their own;
+        //  whoever takes the plane over owns a block a little larger than its table)
+        const size_t plane_bytes = (std::max<size_t>(b->table_size, 1) * sizeof(T) + 15) & ~(size_t) 15;
+        if (!b->direct[0])
+            if (int rc = ek_hip_malloc(plane_bytes + (size_t) b->max_pieces * sizeof(uint32_t), &b->direct[0])) return rc;
+        if (!b->direct[1])
+            if (int rc = ek_hip_malloc(plane_bytes, &b->direct[1])) return rc;
+        b->direct_modes = static_cast<char *>(b->direct[0]) + plane_bytes;
+    } else if (!b->early)
         if (int rc = ek_hip_malloc((size_t) 2 * b->max_pieces * Bins * slot + (fixed ? (size_t) b->max_pieces * sizeof(uint32_t) : 0), &b->early)) return rc;
     // scale: no piece is larger than ~1.5 n / (pieces aimed at) + a page per partition workgroup (k_page_directory cuts a bucket in
     // proportion to its population); the kernel checks its own piece against 2^(62 - S0) and runs it under locks otherwise
     const size_t piece_bound = 2 * (b->n / std::max<size_t>(1, b->max_pieces - (size_t) b->n_buckets)) + 65536;
     const int S0 = std::min(fixed_shift_for(piece_bound), 48);
-    uint32_t *modes = fixed ? reinterpret_cast<uint32_t *>(static_cast<char *>(b->early) + (size_t) 2 * b->max_pieces * Bins * slot) : nullptr;
-    const bool scalar = b->scalar_addend;
+    uint32_t *modes = direct ? (uint32_t *) b->direct_modes
+                    : fixed ? reinterpret_cast<uint32_t *>(static_cast<char *>(b->early) + (size_t) 2 * b->max_pieces * Bins * slot) : nullptr;
+    // (where the kernel writes plane 0 -- the slots, or the first direct table -- and plane 1 of the direct tables: null = slots)
+    T *plane0 = direct ? (T *) b->direct[0] : (T *) b->early, *direct1 = direct ? (T *) b->direct[1] : nullptr;
     // A kept partition that this object found in its caller's cache (a hit) gets its refined stream here, once, outside a capture;
     // the kernel that reads it runs whenever the partition has one -- the scalar-addend kernel too: its refined instantiations fit
     // (106 scalar registers, 121 vector registers, no scratch, no spill: profiles/kernel_resources_refine_r14.txt).
-    const bool eager = refuse_while_capturing_quiet() == EK_OK;
     if (fixed && eager && b->part && b->stands_on_kept && b->part->refine_state == 0 && Bins <= ((size_t) 1 << kRefineEntryBits))
         if (int rc = partition_refine(b->part)) return rc;
     const bool use_refined = fixed && eager && b->part && b->part->refine_state == 1;
@@ -839,9 +917,9 @@ int bucketed_forward_adjoint_launch(Bucketed *b, void *out, int map_op, int keep
             }
             if (use_refined) {
                 hipLaunchKernelGGL(kernel_refined, dim3(b->max_pieces), dim3(kBucketThreads), lds, c.stream,
-                                   (T *) b->reduce_partials, (T *) b->early, (const T *) b->table_a, (const T *) b->table_c, b->table_size,
+                                   (T *) b->reduce_partials, plane0, (const T *) b->table_a, (const T *) b->table_c, b->table_size,
                                    flip_a, flip_c, (const uint16_t *) b->pair_idx, (const T *) b->x_b, b->lists(), map_op, keep_op, b->shift,
-                                   fin, xmax, S0, modes, RefinedStream{ p->refined_x, p->refined_hdr, p->refined_tiles, p->refined_cap_tiles });
+                                   fin, xmax, S0, modes, RefinedStream{ p->refined_x, p->refined_hdr, p->refined_tiles, p->refined_cap_tiles }, direct1);
                 return EK_OK;
             }
         }
@@ -854,9 +932,9 @@ int bucketed_forward_adjoint_launch(Bucketed *b, void *out, int map_op, int keep
                                fin, xmax, S0, modes, NoRefinedStream{});
         } else {
             hipLaunchKernelGGL(kernel, dim3(b->max_pieces), dim3(kBucketThreads), lds, c.stream,
-                               (T *) b->reduce_partials, (T *) b->early, (const T *) b->table_a, (const T *) b->table_c, b->table_size,
+                               (T *) b->reduce_partials, plane0, (const T *) b->table_a, (const T *) b->table_c, b->table_size,
                                flip_a, flip_c, (const uint16_t *) b->pair_idx, (const T *) b->x_b, b->lists(), map_op, keep_op, b->shift,
-                               fin, xmax, S0, modes, NoRefinedStream{});
+                               fin, xmax, S0, modes, NoRefinedStream{}, direct1);
         }
         return EK_OK;
     };
@@ -879,8 +957,10 @@ int bucketed_forward_adjoint_launch(Bucketed *b, void *out, int map_op, int keep
     //  the host can say without a read-back)
     const size_t stream_bytes = use_refined ? 18u * (b->n / 4u + 3u * std::min(b->n, b->table_size) / 8u) : b->n * (sizeof(uint16_t) + sizeof(T));
     EK_LAUNCH_CHECK("bucket_pair_fma_reduce_adjoint", b->n,
-                    stream_bytes + (b->table_c ? 2 : 1) * b->table_size * sizeof(T) + (size_t) 2 * b->max_pieces * Bins * slot);
+                    stream_bytes + (b->table_c ? 2 : 1) * b->table_size * sizeof(T) +
+                    (direct ? 2 * b->table_size * sizeof(T) : (size_t) 2 * b->max_pieces * Bins * slot));
     b->launched_reducing();
+    b->early_direct = direct;
     b->early_fixed = fixed;
     b->early_S0 = S0;
     b->early_modes = modes;

@@ -612,6 +612,11 @@ inline bool early_fixed_enabled() {
     return on;
 }
 
+/// tuning "direct_tables" = 1: the smallest table whose gradient arrays take the kernel's tables over.  The fold this saves moves
+/// 16 B per entry; below 256 Ki entries (4 MB) that is less than its launch costs, and the steps of such tables keep the one launch
+/// per backward() that the launch-count tests of the kept partition pin (K = 64 Ki).  "direct_tables" = 2 ignores the bound.
+constexpr size_t kDirectTablesMinEntries = (size_t) 1 << 18;
+
 // ---- host side -------------------------------------------------------------------------------------
 // What the partition of (index, x, mask) produced, apart from any one expression: the bucket-ordered lists, the page directory
 // and the counter block with its result words.  A function of (index, x, mask, table size, bucket shift, page geometry) only --
@@ -648,7 +653,11 @@ struct ek_hip_bucket_partition {
     uint32_t *refined_tiles = nullptr;
     uint32_t refined_cap_tiles = 0;
     size_t refined_bytes = 0;
-    void free_storage();           // bucketed.hip: the ring block back to the ring (with its `clean` state), the rest to the allocator
+    // is EVERY bucket exactly one piece?  Read back once (piece_prefix), at the first launch of an object that stands on the kept
+    // partition (partition_one_piece(), bucketed_early.hip): each workgroup of the forward + adjoint kernel then owns its bucket's final
+    // sums and writes them in table layout.  A bucket without a piece has nobody to write its range: such a partition says "no".
+    int one_piece_state = 0;       // 0: not asked yet, 1: yes, -1: no
+    void free_storage();          // bucketed.hip: the ring block back to the ring (with its `clean` state), the rest to the allocator
     ~ek_hip_bucket_partition() { free_storage(); }
 };
 namespace ek {
@@ -686,6 +695,13 @@ struct Bucketed {
     bool early_fixed = false;      // `early` holds 64-bit fixed-point sums (8 B per entry and piece) + one mode word per piece behind them
     int early_S0 = 0;              // their scale: terms bounded by 1 times 2^S0 (fixed_scale())
     uint32_t *early_modes = nullptr;   // device, [max_pieces]: 0 fixed point, 1 floats (a piece that ran under locks)
+    // DIRECT tables (a kept partition of one-piece buckets, tuning "direct_tables"): the kernel wrote plane c -- floats, finished as the
+    // fold finishes them for a fresh table at scale 1 -- into direct[c][0 .. table_size) instead of the slots of `early`.  Two allocations:
+    // each may become a gradient array of its own (ek_hip_bucketed_take_tables); what nobody took is freed with the object.
+    void *direct[2] = { nullptr, nullptr };
+    bool early_direct = false;         // the sums of the last forward + adjoint launch are in `direct`, not in `early`
+    void *direct_modes = nullptr;      // the mode words of such a launch (written by the kernel, read by nobody): behind plane 0, in ITS block -- not owned
+    bool addend_broadcast = false;     // table_c is a device scalar broadcast into a table the object owns (ek_hip_bucketed_addend_adjoint reads slots)
     // paged lists (ek_paged.h; 4-byte element types): page_shift = 5 | 6, pair_idx / x_b / u_b / m_b hold `positions` elements
     // (whole pages, the workgroups' unused slots in between), bucket_base counts complete pages
     int page_shift = 0;

@@ -37,6 +37,9 @@ struct Tuning {
                                   // ek_hip_bucketed_pair_create_on); 0: both answer EK_ERR_UNSUPPORTED, every object partitions for itself
     int partition_refine = 1;     // a kept partition gets a refined stream (entry order, groups of four: ek_refine.h) at its first hit:
                                   // 0 never, 1 when the lookups per entry make it pay, 2 whenever the shape is covered (tests)
+    int direct_tables = 1;        // on a kept partition whose buckets are ONE piece each the forward + adjoint kernel writes its sums in
+                                  // table layout and a fresh gradient array takes the tables over (ek_hip_bucketed_take_tables): 0 never
+                                  // (slots + fold), 1 for tables of kDirectTablesMinEntries entries and more, 2 whenever the shape is covered (tests)
     int sort_radix = 1;           // ek_hip_sort (sort.hip): 0 always forwards to ek_hip_sort_blocks, 1 radix passes from the measured crossover
                                   // on, 2 radix passes for every n >= 2 (tests)
     int xcd_balance = 0;          // 1: the page partition deals its tiles to the workgroup classes w % 8 by fed-back weights (ek_paged.h);

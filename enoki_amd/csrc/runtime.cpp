@@ -244,6 +244,7 @@ int ek_hip_init(int device) {
     if (const char *ea = getenv("ENOKI_HIP_EARLY_ADJOINT")) c.tuning.early_adjoint = atoi(ea) != 0;
     if (const char *pc = getenv("ENOKI_HIP_PARTITION_CACHE")) c.tuning.partition_cache = atoi(pc) != 0;
     if (const char *pr = getenv("ENOKI_HIP_PARTITION_REFINE")) { int v = atoi(pr); if (v >= 0 && v <= 2) c.tuning.partition_refine = v; }
+    if (const char *dt = getenv("ENOKI_HIP_DIRECT_TABLES")) { int v = atoi(dt); if (v >= 0 && v <= 2) c.tuning.direct_tables = v; }
     if (const char *xb = getenv("ENOKI_HIP_XCD_BALANCE")) c.tuning.xcd_balance = atoi(xb) == 2 ? 2 : atoi(xb) != 0;
     if (const char *gr = getenv("ENOKI_HIP_GATHER_RECORDS")) { int v = atoi(gr); if (v >= 0 && v <= 2) c.tuning.gather_records = v; }
     if (c.log_level >= 1)
@@ -637,6 +638,7 @@ int ek_hip_set_tuning(const char *key, int value) {
     else if (!strcmp(key, "early_adjoint") && (value == 0 || value == 1)) t.early_adjoint = value;
     else if (!strcmp(key, "partition_cache") && (value == 0 || value == 1)) t.partition_cache = value;
     else if (!strcmp(key, "partition_refine") && value >= 0 && value <= 2) t.partition_refine = value;
+    else if (!strcmp(key, "direct_tables") && value >= 0 && value <= 2) t.direct_tables = value;
     else if (!strcmp(key, "sort_radix") && value >= 0 && value <= 2) t.sort_radix = value;
     else if (!strcmp(key, "xcd_balance") && value >= 0 && value <= 2) t.xcd_balance = value;
     else return fail(EK_ERR_INVALID, "ek_hip_set_tuning(): unknown key/value %s=%d", key, value);

@@ -492,6 +492,12 @@ namespace detail {
         void adopt_uninitialized() {
             evaluate("HIPArray (zeros)", [](void *) { return (int) EK_OK; });
         }
+        /// A pending zeros node becomes the owner of storage that already holds what its only consumer would have written into it
+        /// (`p`: from ek_hip_malloc, `size` elements -- ek_hip_bucketed_take_tables): no allocation, no memset, no kernel
+        void adopt_pointer(void *p) {
+            ptr = p;
+            drop_deferred();
+        }
 
         /// Execute the deferred gather / map
         void force() {
@@ -1661,6 +1667,22 @@ template <typename Value_> struct HIPArray : ArrayTag {
         if (!u->deferred) return false;
         ek_hip_bucketed *b = u->bucketed();
         if (!b) return false;
+        if (&ek_hip_bucketed_take_tables && count <= 2) {
+            // every target a fresh gradient buffer, every factor 1 -- backward(hsum(..)) -- and the forward pass left exactly these
+            // sums per table entry in tables of their own (a kept partition of one-piece buckets): the buffers ARE those tables from
+            // here on, no kernel runs.  All or nothing; EK_ERR_UNSUPPORTED changes nothing and the fold below runs as ever.
+            bool all = true;
+            for (size_t c = 0; c < count; ++c) all = all && fresh[c] && scale[c] == imm_bits(Value(1));
+            if (all) {
+                void *taken[2] = { nullptr, nullptr };
+                int rc = ek_hip_bucketed_take_tables(b, (int) count, from_u, ops, weighted, scale, taken);
+                if (rc == EK_OK) {
+                    for (size_t c = 0; c < count; ++c) targets[c]->m_buf->adopt_pointer(taken[c]);
+                    return true;
+                }
+                if (rc != EK_ERR_UNSUPPORTED) detail::hip_check(rc, "scatter_add_multi_ (bucket order)");
+            }
+        }
         for (size_t c = 0; c < count; ++c) {
             if (fresh[c]) targets[c]->m_buf->adopt_uninitialized();
             bases[c] = targets[c]->m_buf->ptr;

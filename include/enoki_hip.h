@@ -167,7 +167,7 @@ EK_API int ek_hip_graph_end(ek_hip_graph **out);
 EK_API int ek_hip_graph_launch(ek_hip_graph *graph);
 EK_API uint64_t ek_hip_graph_launch_count(const ek_hip_graph *graph);   /* kernel launches inside one replay */
 EK_API int ek_hip_graph_destroy(ek_hip_graph *graph);
-EK_API int ek_hip_set_tuning(const char *key, int value);   /* "reduce_blocks_per_cu", "scatter_add_binned", "deterministic", "gather_records", "bucket_ordered", "early_adjoint", "partition_cache", "partition_refine" (0 never, 1 automatic, 2 whenever the shape is covered), "sort_radix" (ek_hip_sort: 0 never the radix route, 1 automatic, 2 for every n >= 2) */
+EK_API int ek_hip_set_tuning(const char *key, int value);   /* "reduce_blocks_per_cu", "scatter_add_binned", "deterministic", "gather_records", "bucket_ordered", "early_adjoint", "partition_cache", "partition_refine" (0 never, 1 automatic, 2 whenever the shape is covered), "direct_tables" (ek_hip_bucketed_take_tables: 0 never, 1 for tables of 256 Ki entries and more, 2 whenever the shape is covered), "sort_radix" (ek_hip_sort: 0 never the radix route, 1 automatic, 2 for every n >= 2) */
 /* Per-kernel timing: between begin and end one HIP event is recorded on the library stream after every
    launch.  ek_hip_profile_end() synchronizes and returns a malloc'd JSON array (caller free()s) of
    {"kernel", "launches", "total_ms", "bytes", "elements"}; `bytes` are the ALGORITHMIC bytes of the
@@ -378,6 +378,18 @@ EK_API int ek_hip_bucketed_scatter_add_scaled(ek_hip_bucketed *b, int count, voi
 /* != 0: a hinted object sums keep_op(u) and x * keep_op(u) per table entry inside reduce(EK_HSUM, map_op, keep, keep_op):
  * {sin, cos}, {cos, sin}, {log, rcp} and {f, f} for f in neg abs sqrt rcp rsqrt sin cos exp log */
 EK_API int ek_hip_bucketed_early_pair(int map_op, int keep_op);
+/* The adjoint without a kernel.  On a kept partition whose buckets are ONE piece each (tuning "direct_tables", ENOKI_HIP_DIRECT_TABLES:
+ * 1, the default, for tables of 256 Ki entries and more; 2 for every table; 0 never) the forward + adjoint kernel of a hinted object writes the sums of keep_op(u) and of x * keep_op(u) per
+ * table entry in table layout, finished as ek_hip_bucketed_scatter_add would finish them in a FRESH table at scale 1 -- bit for bit.
+ * When the scatter_add that backward() is about to issue is exactly those streams (count 1 or 2: the plain and / or the weighted one,
+ * from_u / map_ops / weighted as for scatter_add), every scale_bits[s] is 1.0f (NULL: all ones) and every target is fresh, the caller
+ * takes the tables over instead: tables[s] receives stream s's buffer of table_size floats, allocated by ek_hip_malloc -- the caller
+ * owns it from then on and frees it with ek_hip_free.  The object forgets the sums: a second request is answered
+ * EK_ERR_UNSUPPORTED and the scatter_add that follows evaluates the streams on the lists.  Tables nobody takes are freed with the object.
+ * EK_ERR_UNSUPPORTED (no error message; nothing changed): not that situation -- call ek_hip_bucketed_scatter_add_scaled as before.
+ * EK_OPTIONAL: without the entry enoki/hip.h folds every step. */
+EK_API EK_OPTIONAL int ek_hip_bucketed_take_tables(ek_hip_bucketed *b, int count, const int *from_u, const int *map_ops, const int *weighted,
+                                                   const uint64_t *scale_bits, void **tables);
 /* diagnostics: how the partition cut the object's buckets -- *pieces: pieces that exist (all slices of a large table together),
  * *largest: the most pieces any ONE bucket was cut into (1: every populated bucket is one piece; the per-piece tables of the early
  * sums then hold floats, see ek_hip_bucketed_scatter_add).  Reads the piece prefix back: synchronises, refuses while a step graph
